@@ -1,6 +1,6 @@
 """bench.py — fusion-level DynMM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one synthetic batch resident in HBM: zero grads, forward (dual
@@ -8,12 +8,16 @@ ResNet-34 NonBottleneck1D encoders, SE fusion, global gate with soft DiffSoftmax
 decoder, 4 training outputs), weighted multi-scale CE + FLOP regulariser, full backward, [gradient all-reduce],
 fused SGD-Nesterov update — batch 32/GPU at 480x640 (BASELINE.json configs[2], the configuration `metric` is
 quoted on).  N>1 = pure data parallel, weak scaling, gradient buckets all-reduced over RCCL while backward is
-still running.  Prints ONE JSON line on rank 0; besides the contract's fields it carries
+still running.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times K steps (`ms_per_step`), writes the last timed step's outputs if
+--dump-outputs is given, and prints the line.  With --full the line also carries
   roofline      dominant implicit-GEMM kernel vs the fp32 MFMA peak (HIP events on the launch stream),
   cpu_baseline  the CPU oracle (a port of the reference's PyTorch CPU path) on this host's cores,
   parity        the HIP step vs that same oracle run (logits, losses, gradient cosine) — same inputs,
   extra         configs[1] (fwd-only, batch 16, gate forced on) and configs[3]-style hard-gate lines measured
-                in the same process.
+                in the same process,
+and the box diagnostics (`config.dependent_kernel_interval_us`; N>1: the step without collectives, rank skew).
 """
 import argparse
 import json
@@ -40,6 +44,7 @@ TRAFFIC_NOTE = ('HBM bytes per launch from profiles/pmc_dominant_kernel.json (se
                 'for kernels that stream 16 B/lane (conv_wgrad_v4, conv_igemm_v5), 1 = raw for the 4 B/lane gathers of the implicit-GEMM '
                 'kernels (uncalibrated width: lower bound).  For the split weight gradient the figure includes its slab '
                 'writes; the slab reduction kernel that follows is listed separately in the JSON.')
+DUMP_SAMPLE = 1 << 21             # --dump-outputs: elements kept of a larger output (8 MB per array in float32)
 
 
 def parse():
@@ -76,6 +81,12 @@ def parse():
                     help="N > 1 over RCCL: the stream the gradient-bucket all-reduces are enqueued on (dp.GradBucketReducer): the last "
                          "weight-gradient stream (default), the depth-encoder stream, or asynchronous collectives from a "
                          "communication stream of their own")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; an output '
+                         f'of more than {DUMP_SAMPLE} elements as a fixed, seeded sample of them)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the secondary measurements and checks: roofline, CPU baseline + parity, extra lines, box '
+                         'diagnostics (each still switched off by its --no-* option)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-batch', type=int, default=4, help='batch of the thread sweep + parity sample')
     ap.add_argument('--no-cpu-full-batch', dest='cpu_full_batch', action='store_false',
@@ -84,7 +95,10 @@ def parse():
     ap.add_argument('--no-extra', action='store_true', help='skip the secondary lines (configs[1] fwd-only, hard-gate)')
     ap.add_argument('--affect-only', action='store_true',
                     help='print the ModalityDynMM (configs[4]) secondary line alone: what the main run starts as a child process')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def make_model(cfg, h, w, device, kind='gate'):
@@ -110,6 +124,31 @@ def make_batch(n, h, w, device, seed):
 
 def branches_for(kind, n):
     return [(i % 5) if kind == 'uniform' else (4 if kind == 'all4' else 0) for i in range(n)]
+
+
+def step_outputs(result, ts, model):
+    """name -> tensor: what a caller of the timed path receives from its last step.  Training: the step's losses, and the state
+    the step leaves behind (updated parameters, the gradient it computed, BatchNorm running statistics).  Forward: the model's
+    outputs."""
+    if ts is None:
+        parts = [result] if torch.is_tensor(result) else [t for t in result if torch.is_tensor(t)]
+        return {'logits' if len(parts) == 1 else f'out{i}': t for i, t in enumerate(parts)}
+    running = [v.reshape(-1) for k, v in model.state_dict().items() if 'running_' in k]
+    return {'losses': result['losses'], 'loss_flop': result['loss_flop'], 'total': result['total'],
+            'params': ts.flatp.flat, 'grads': ts.reducer.flat, 'bn_running_stats': torch.cat(running)}
+
+
+def dump_outputs(path, arrays):
+    """Each array as path/<name>.npy in float32.  One of more than DUMP_SAMPLE elements is replaced by the same sample of its
+    (flattened) elements in every run: sorted indices from a generator of fixed seed."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, f'{name}.npy'), t.cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -452,12 +491,13 @@ def timed(step, steps, warmup, world, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    timed.last = last                                 # what the last timed step returned (--dump-outputs)
     timed.per_rank = [elapsed]
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -502,7 +542,7 @@ def train_workload(args, device, rank, world, hard=False, branches='all4', compa
                           exchange=args.dp_exchange)
 
     def step():
-        ts(rgb, depth, labels)
+        return ts(rgb, depth, labels)
 
     def body_only():
         """forward + loss + backward of THIS rank only — no collective, no update: what the per-kernel timing pass runs
@@ -758,6 +798,10 @@ def main():
     elapsed = timed(step, args.steps, args.warmup, world, device)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = args.batch * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # before anything below runs the model again (the instrumented step, the N > 1 exchange-cost steps)
+        dump_outputs(args.dump_outputs, step_outputs(timed.last, ts, model))
+    timed.last = None
 
     dp_info = None
     if world > 1:
@@ -774,6 +818,7 @@ def main():
         red = ts.reducer
         dp_info.update({'buckets': len(red.buckets), 'launched_during_backward': red.launched_in_backward,
                         'bucket_mb': round(4 * max(e - s for s, e in red.buckets) / 2 ** 20, 1)})
+    if ts is not None and world > 1 and args.full:
         # what the exchange costs: the same step with the reducer switched off (no collective, local gradients), and
         # each rank's own loop time with no barrier at the end (rank skew)
         k2 = max(3, args.steps // 2)
@@ -804,7 +849,7 @@ def main():
 
     census = ts.census if ts is not None else None        # of the timed loop's last step (the instrumented pass below is single-stream)
     roofline = None
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and args.full and not args.no_kernel_timing:
         if ts is not None:
             saved = (ts.multi_stream, getattr(model, 'dual_stream', False), ts.use_graph)
             ts.multi_stream, model.dual_stream, ts.use_graph = False, False, False
@@ -820,7 +865,7 @@ def main():
     torch.cuda.empty_cache()
 
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra and train and not args.hard and args.model == 'gate':
+    if rank == 0 and world == 1 and args.full and not args.no_extra and train and not args.hard and args.model == 'gate':
         extra = {}
         # configs[1]: fwd-only, batch 16, static fuse (gate forced on) — measured by the same driver run
         extra['fwd_only'] = measure_fwd(args, device, 16, 'all4', True, max(10, args.steps), 3)
@@ -877,7 +922,7 @@ def main():
             torch.cuda.empty_cache()
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu, parity = cpu_baseline_and_parity(args, device)
 
     if rank == 0:
@@ -918,7 +963,7 @@ def main():
                        'stream_plan': ops.stream_plan(device).report,      # do the plan's streams run side by side (pair probe)?
                        'optimizer_in_step': 'fused SGD-Nesterov' if train else None,
                        'winograd': {'passes': ops.WINO, 'input_gradients': ops.WINO_DGRAD, 'weight_gradients': True},
-                       'dependent_kernel_interval_us': dependent_kernel_interval_us(device),
+                       'dependent_kernel_interval_us': dependent_kernel_interval_us(device) if args.full else None,
                        'dp': dp_info},
             'whole_step': {'net': f'{"SkipGateESANet" if args.model == "gate" else "SkipESANet"} R34-'
                                   f'{"NBt1D" if args.config == "P" else "BasicBlock"} SE-add (config {args.config})',

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r04
 rm -rf $O; mkdir -p $O
 B="--no-cpu-baseline --no-extra"
-rocprofv3 --kernel-trace --stats -d $O/single -o bench -- python $R/bench.py --steps 3 --warmup 1 $B --single-stream > $O/single_stdout.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/single -o bench -- python $R/bench.py --full --steps 3 --warmup 1 $B --single-stream > $O/single_stdout.log 2>&1
 # (--no-kernel-timing: the LAST step of the trace must be a step of the timed loop, not the single-stream instrumented one)
 rocprofv3 --kernel-trace --stats -d $O/multi -o bench -- python $R/bench.py --steps 3 --warmup 1 $B --no-kernel-timing > $O/multi_stdout.log 2>&1
 cd $R

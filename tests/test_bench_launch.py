@@ -58,6 +58,22 @@ def test_world_size_mismatch_is_refused():
     assert r.returncode != 0 and 'WORLD_SIZE=1' in (r.stderr + r.stdout)
 
 
+def test_dump_outputs_are_the_same_float32_sample_every_run(tmp_path):
+    """--dump-outputs: every file float32; an output of more than DUMP_SAMPLE elements becomes the same sample of its elements in
+    every run (sorted indices spread over the whole array), so the dumps of two builds compare element for element."""
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(3 * bench.DUMP_SAMPLE, dtype=torch.float64)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), {'big': big, 'small': torch.ones(2, 3, dtype=torch.float16)})
+    a, b = np.load(tmp_path / 'a' / 'big.npy'), np.load(tmp_path / 'b' / 'big.npy')
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,) and (a == b).all()
+    assert (np.diff(a) >= 0).all() and a.min() < bench.DUMP_SAMPLE and a.max() >= 2 * bench.DUMP_SAMPLE
+    small = np.load(tmp_path / 'a' / 'small.npy')
+    assert small.dtype == np.float32 and small.shape == (2, 3) and (small == 1).all()
+
+
 def test_roofline_kernel_names_match_the_pmc_summary():
     """bench.py quotes the roofline per compiled kernel instance (kernel_instance) and looks its HBM traffic up under that name in
     profiles/pmc_dominant_kernel.json, which profiles/summarize_pmc.py writes: the two name tables must agree, or `traffic`
