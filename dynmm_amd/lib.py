@@ -159,6 +159,12 @@ SIGNATURES = {
     'dynmm_moe_head': (c_i, [c_f, _PP, c_i, c_f, c_fl, c_i, c_fl, c_f, c_f, c_f, _PP, c_f, c_i, c_f]),
     'dynmm_clip_grad_norm_workspace_bytes': (c_sz, []),
     'dynmm_clip_grad_norm': (c_i, [c_f, c_sz, c_fl, c_f, c_f, c_f]),
+    'dynmm_maxout_bn_fwd': (c_i, [c_f] * 9 + [c_i, c_i, c_i, c_fl, c_fl, c_i, _DP, c_f]),
+    'dynmm_maxout_bn_bwd': (c_i, [c_f] * 8 + [c_i, c_i, c_i, c_i, _DP, c_f]),
+    'dynmm_ml_head': (c_i, [c_f, _PP, c_i, c_i, c_f, c_fl, c_i, c_fl, c_f, c_f, c_f, _PP, c_f, c_i, c_f]),
+    'dynmm_ml_blend_bwd': (c_i, [c_f, c_f, c_f, _PP, c_i, c_i, c_f, c_fl, _PP, c_f, c_i, c_f]),
+    'dynmm_ml_counts': (c_i, [c_f, c_f, c_i, c_i, c_f, c_f, c_f]),
+    'dynmm_ml_partition': (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f]),
 }
 
 ABI_VERSION = 4

@@ -586,6 +586,37 @@ size_t dynmm_clip_grad_norm_workspace_bytes(void);
 int dynmm_clip_grad_norm(const float* flat_grad, size_t n, float max_norm, double* workspace, float* norm_and_coef,
                          void* stream);
 
+/* ---- modality-level DynMM on MM-IMDB features (ModalityDynMM/multimedia/imdb_dyn.py), csrc/mlp.hip ---- */
+/* MultiBench Maxout(k=2) -> BatchNorm1d -> Dropout on z [B, 2M] (maxout = 1: output j = max(z[:, 2j], z[:, 2j+1])) or
+ * BatchNorm1d on z [B, M] (maxout = 0, no dropout by the caller's choice); y [B, M].  train = 1: batch statistics (B >= 2),
+ * running_mean / running_var (either may be NULL) updated with `momentum` and the unbiased variance, num_batches_tracked
+ * (NULL allowed) += 1, dropout `drop` (indices over y's [B, M] layout).  train = 0: running statistics, no dropout.
+ * save_mean / save_rstd [M] receive the normalisation for the backward. */
+int dynmm_maxout_bn_fwd(const float* z, float* y, float* save_mean, float* save_rstd, float* running_mean, float* running_var,
+                        long long* num_batches_tracked, const float* gamma, const float* beta, int B, int M, int maxout,
+                        float eps, float momentum, int train, const dynmm_dropout* drop, void* stream);
+/* backward: dgamma / dbeta [M] (either may be NULL) = sum over the batch, written (not accumulated); dz [B, 2M] (maxout) or
+ * [B, M] (NULL allowed): the input gradient, 0 on the losing column of each pair. */
+int dynmm_maxout_bn_bwd(const float* dy, const float* z, const float* save_mean, const float* save_rstd, const float* gamma,
+                        float* dz, float* dgamma, float* dbeta, int B, int M, int maxout, int train, const dynmm_dropout* drop,
+                        void* stream);
+/* Multilabel mixture head: w = DiffSoftmax(logits[B,K]/temp, hard), out[B,C] = sum_k w_k preds[k], aux = mean w[:,K-1];
+ * with target [B,C] != NULL: loss = mean BCEWithLogits(out, target), scalars = {loss, aux, loss + reg*aux} and the backward
+ * seeds d_preds[k] [B,C] (optional per k) and d_logits [B,K] (NULL allowed); without: scalars = {0, aux, reg*aux}.  K <= 4.
+ * preds = NULL: the gate alone (weight and scalars; out and target unused). */
+int dynmm_ml_head(const float* logits, const float* const* preds, int K, int C, const float* target, float temp, int hard,
+                  float reg, float* out, float* weight, float* scalars, float* const* d_preds, float* d_logits, int B,
+                  void* stream);
+/* backward of the blend alone for upstream gradients d_out [B,C] / d_aux [1] (either may be NULL). */
+int dynmm_ml_blend_bwd(const float* d_out, const float* d_aux, const float* logits, const float* const* preds, int K, int C,
+                       const float* weight, float temp, float* const* d_preds, float* d_logits, int B, void* stream);
+/* evaluation counts: pred = round(sigmoid(logits)), y = target > 0.5; counts [3][C] += (TP, FP, FN) per class; loss_sum[0]
+ * (NULL allowed) += sum of BCEWithLogits(logits, target).  C <= 256. */
+int dynmm_ml_counts(const float* logits, const float* target, int B, int C, int* counts, double* loss_sum, void* stream);
+/* hard-gate partition: branch[b] = first arg-max of weight[b, :K]; order [B] = samples grouped by branch, ascending and
+ * stable; inv [B] = inverse permutation; counts [K]. */
+int dynmm_ml_partition(const float* weight, int K, int B, int* order, int* inv, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
