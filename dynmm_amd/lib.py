@@ -165,6 +165,7 @@ SIGNATURES = {
     'dynmm_ml_blend_bwd': (c_i, [c_f, c_f, c_f, _PP, c_i, c_i, c_f, c_fl, _PP, c_f, c_i, c_f]),
     'dynmm_ml_counts': (c_i, [c_f, c_f, c_i, c_i, c_f, c_f, c_f]),
     'dynmm_ml_partition': (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f]),
+    'dynmm_posneg_counts': (c_i, [c_f, c_i, c_f, c_i, c_f, C.c_double, c_i, c_f, c_f, c_f]),
 }
 
 ABI_VERSION = 4

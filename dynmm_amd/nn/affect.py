@@ -22,12 +22,18 @@ in_proj_weight`, ...), so `expert.state_dict()` of a trained MultiBench module l
 (p = 0.1 inside nn.TransformerEncoderLayer) is applied in training mode at torch's four sites per layer, with a Philox
 stream of its own (ops.manual_seed; torch's generator cannot be reproduced bit for bit, the tests inject the keep flags
 on both sides); `.eval()` switches it off as in torch.
+
+Hard-gate inference runs each expert only on the samples routed to it (`compact`, on by default): the gate transformer runs on
+the whole batch, its one-hot decisions are recorded as the dense path records them, the samples are grouped by expert on the
+device (ops_mlp.partition), one host read fetches the group sizes, and each expert runs on its rows alone (an expert with no
+row launches nothing).  Training, the soft gate, infer_mode != 0 and anything under autograd keep the dense path.
 """
 
 import torch
 import torch.nn as nn
 
 from .. import ops
+from .. import ops_mlp as M
 from .. import ops_seq as S
 
 FEATURES = {'visual': 35, 'audio': 74, 'text': 300}      # CMU-MOSEI (affect/count_flop.py:52)
@@ -176,6 +182,8 @@ def late_fusion_transformer():
 
 
 class _GatedMixture(nn.Module):
+    compact = True          # hard-gate eval runs each expert on its own samples only (False: the dense blend, for A/B runs)
+
     def _init_gate(self, branch_num, temp, hard_gate):
         self.branch_num = branch_num
         self.gate = nn.Sequential(Transformer(409, 10), nn.Linear(10, branch_num))       # affect_dyn.py:41,120
@@ -183,6 +191,7 @@ class _GatedMixture(nn.Module):
         self.weight_list = torch.Tensor()
         self.store_weight = False
         self.infer_mode = 0
+        self.last_counts = None            # per-expert sample counts of the last compacted forward
 
     @staticmethod
     def freeze_branch(m):
@@ -215,6 +224,50 @@ class _GatedMixture(nn.Module):
             out, aux, _ = S.moe_blend(torch.zeros_like(logits), preds, self.temp, False)
         return out, aux
 
+    # ---- hard-gate compaction ----------------------------------------------------------------------------------------
+    def _compacting(self):
+        return (self.compact and not self.training and self.hard_gate and self.infer_mode == 0 and
+                not torch.is_grad_enabled())
+
+    def _route(self, inputs):
+        """The gate on every sample, its weight recorded as _mix records it, the samples grouped by expert.  Returns
+        (aux [1], inv [B], counts [K], device rows [K], host rows [K]) after ONE device -> host read (counts and order)."""
+        weight, aux = M.gate_weight(self.gate_logits(inputs), self.temp, True)
+        order, inv, counts = M.partition(weight)            # (enqueued before the recording below waits for the device)
+        if self.store_weight:
+            self.weight_list = torch.cat((self.weight_list, weight.detach().cpu()))
+        K = weight.shape[1]
+        host = torch.cat([counts, order]).cpu()
+        n = [int(v) for v in host[:K]]
+        self.last_counts = tuple(n)
+        rows_d, rows_h, off = [], [], 0
+        for k in range(K):
+            rows_d.append(order[off:off + n[k]])
+            rows_h.append(host[K + off:K + off + n[k]].long())
+            off += n[k]
+        return aux, inv, n, rows_d, rows_h
+
+    @staticmethod
+    def _rows(inputs, modalities, rows_d, rows_h):
+        """[[x_i[rows]], [lengths_i[rows]]] for the listed modalities i (x_i [B, T, F] on the device; the lengths follow the
+        same rows wherever they live)."""
+        xs = [ops.batch_gather(inputs[0][i], rows_d) for i in modalities]
+        lens = []
+        for i in modalities:
+            ln = inputs[1][i]
+            if torch.is_tensor(ln):
+                lens.append(ln[rows_d.long()] if ln.is_cuda else ln[rows_h])
+            else:
+                lens.append([ln[j] for j in rows_h.tolist()])
+        return [xs, lens]
+
+    @staticmethod
+    def _merge(parts, inv):
+        """The experts' [n_k, 1] outputs (in expert order) back in the batch's order."""
+        if len(parts) == 1:
+            return parts[0]                         # every sample took one expert: order and inv are the identity
+        return ops.batch_gather(torch.cat(parts, dim=0), inv)
+
 
 class DynMMNetV2(_GatedMixture):
     """affect_dyn.py:107-175.  The reference loads pickled experts (`torch.load(model_name_list[i])`); here they are
@@ -245,7 +298,26 @@ class DynMMNetV2(_GatedMixture):
         return enc[0], [self.text_head(enc[1]), b2.head(b2.fuse(enc[2:]))]
 
     def forward(self, inputs):
+        if self._compacting():
+            return self._forward_compact(inputs)
         return self._mix(*self.gate_and_experts(inputs))
+
+    def _forward_compact(self, inputs):
+        """Expert 1 (text transformer + head) on its rows' text, expert 2 (the late-fusion model) on its rows' three modalities,
+        the four transformers side by side."""
+        aux, inv, n, rows_d, rows_h = self._route(inputs)
+        b2 = self.branch2
+        fns = []
+        if n[0]:
+            s1 = self._rows(inputs, (2,), rows_d[0], rows_h[0])
+            fns.append(lambda: self.text_head(self.text_encoder([s1[0][0], s1[1][0]])))
+        if n[1]:
+            fns += b2.branch_fns(self._rows(inputs, (0, 1, 2), rows_d[1], rows_h[1]))
+        outs = run_branches(fns)
+        parts = [outs[0]] if n[0] else []
+        if n[1]:
+            parts.append(b2.head(b2.fuse(outs[1 if n[0] else 0:])))
+        return self._merge(parts, inv), aux[0]
 
     def weight_stat(self):
         tmp = torch.mean(self.weight_list, dim=0)
@@ -265,6 +337,9 @@ class DynMMNet(_GatedMixture):
             self.freeze_branch(self.encoders)
             self.freeze_branch(self.heads)
         self._init_gate(3, temp, hard_gate)
+        # MMAC per sample of each expert for cal_flop (the reference's DynMMNet defines none): the text expert is DynMMNetV2's
+        # expert 1 (affect_dyn.py:126); the visual / audio experts differ from it only in the Conv1d (F -> 120 over 50 steps)
+        self.flop = torch.Tensor([135.13226 - (300 - f) * 120 * 50 / 1e6 for f in (35, 74, 300)])
 
     def experts(self, inputs):
         return [self.heads[i](self.encoders[i]([inputs[0][i], inputs[1][i]])) for i in range(3)]
@@ -275,7 +350,23 @@ class DynMMNet(_GatedMixture):
         return outs[0], outs[1:]
 
     def forward(self, inputs):
+        if self._compacting():
+            return self._forward_compact(inputs)
         return self._mix(*self.gate_and_experts(inputs))
+
+    def _forward_compact(self, inputs):
+        """Expert k (modality k's transformer + head) on its rows of modality k, side by side."""
+        aux, inv, n, rows_d, rows_h = self._route(inputs)
+        fns = [lambda k=k, s=self._rows(inputs, (k,), rows_d[k], rows_h[k]): self.heads[k](self.encoders[k]([s[0][0], s[1][0]]))
+               for k in range(3) if n[k]]
+        return self._merge(run_branches(fns), inv), aux[0]
+
+    def weight_stat(self):
+        """mean gate weight per expert; returns the text expert's (the one the regulariser penalises, affect_dyn.py:96)."""
+        tmp = torch.mean(self.weight_list, dim=0)
+        print(f'mean branch weight {tmp[0].item():.4f}, {tmp[1].item():.4f}, {tmp[2].item():.4f}')
+        self.store_weight = False
+        return tmp[2].item()
 
 
 class AffectTrainStep:

@@ -411,3 +411,67 @@ def clip_grad_norm(flat_grad, max_norm):
     L.check(lib.dynmm_clip_grad_norm(_p(flat_grad), C.c_size_t(flat_grad.numel()), float(max_norm), ws.data_ptr(), _p(out),
                                      _stream()), 'clip_grad_norm')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# evaluation: Supervised_Learning.single_test, task "posneg-classification" — 2x2 counts and the loss accumulator on the
+# device, Accuracy / Loss / Corr on the host from one read
+# ---------------------------------------------------------------------------------------------------------------
+class PosnegCounts:
+    """The reference's posneg evaluation of one pass, accumulated on the device (one launch per batch, no host sync).
+
+    form 'test' (single_test with criterion L1Loss(reduction='sum'), affect_dyn.py:228,233): each batch adds
+    len(batch) * sum|out - y| — the reference multiplies the SUM by the batch size once more, so its reported Loss is
+    sum_batches B_i * sum_i|out - y| / N, not the mean absolute error.  The quirk is kept: the numbers match the reference's.
+    form 'valid' (train's validation, Supervised_Learning.py:160-185, objective L1Loss()): each batch adds
+    (mean|out - y| + lossw * aux) * len(batch), aux = the gate regulariser the model returned with the batch."""
+
+    FORMS = {'test': 0, 'valid': 1}
+
+    def __init__(self, device, form='test', lossw=0.0):
+        if form not in self.FORMS:
+            raise ValueError(f'form must be one of {sorted(self.FORMS)}, got {form!r}')
+        self.form, self.lossw = form, float(lossw)
+        self.counts = torch.zeros(4, device=device, dtype=torch.int64)
+        self.loss_acc = torch.zeros(1, device=device, dtype=torch.float64)
+        self.n = 0
+
+    def add(self, out, target, aux=None):
+        out = _chk(out.detach(), 'out')
+        tgt = _chk(target.detach().float(), 'target')
+        B = out.shape[0]
+        if out.dim() not in (1, 2) or out.numel() == 0 or tgt.numel() != B:
+            raise L.DynmmHipError(f'posneg counts: out must be [B] or [B, C] and target hold B values, got out '
+                                  f'{tuple(out.shape)}, target {tuple(tgt.shape)}')
+        stride = 1 if out.dim() == 1 else out.shape[1]
+        a = None
+        if self.form == 'valid' and torch.is_tensor(aux):
+            a = _chk(aux.detach().reshape(1).float(), 'aux')
+        L.check(_lib().dynmm_posneg_counts(_p(out), stride, _p(tgt), B, _p(a), self.lossw, self.FORMS[self.form],
+                                           self.counts.data_ptr(), self.loss_acc.data_ptr(), _stream()), 'posneg_counts')
+        self.n += B
+
+    def read(self):
+        """{'counts': int64 numpy [n00, n01, n10, n11] (index 2 * (out >= 0) + (y >= 0)), 'loss_acc', 'n'} — the one
+        device -> host transfer of a pass."""
+        host = torch.cat([self.counts.double(), self.loss_acc]).cpu().numpy()
+        return {'counts': host[:4].astype('int64'), 'loss_acc': float(host[4]), 'n': self.n}
+
+    def metrics(self):
+        r = self.read()
+        return posneg_metrics(r['counts'], r['loss_acc'], r['n'])
+
+
+def posneg_metrics(counts, loss_acc, n):
+    """single_test's posneg summary from the 2x2 counts [n00, n01, n10, n11] (index 2 * pred + truth):
+    {'Accuracy': (n11 + n00) / N, 'Loss': loss_acc / N, 'Corr': pearsonr(truth, pred)}.  The Pearson correlation of two 0/1
+    vectors is the phi coefficient of their 2x2 table; NaN when a marginal is zero (a constant vector), as scipy gives."""
+    n00, n01, n10, n11 = (int(v) for v in counts)
+    N = n00 + n01 + n10 + n11
+    if N != int(n):
+        raise ValueError(f'the counts hold {N} samples, expected {n}')
+    if N == 0:
+        return {'Accuracy': float('nan'), 'Loss': float('nan'), 'Corr': float('nan')}
+    den = (n10 + n11) * (n00 + n01) * (n01 + n11) * (n00 + n10)       # pred = 1, pred = 0, truth = 1, truth = 0
+    corr = (n11 * n00 - n10 * n01) / den ** 0.5 if den > 0 else float('nan')
+    return {'Accuracy': (n11 + n00) / N, 'Loss': float(loss_acc) / N, 'Corr': float(corr)}

@@ -617,6 +617,15 @@ int dynmm_ml_counts(const float* logits, const float* target, int B, int C, int*
  * stable; inv [B] = inverse permutation; counts [K]. */
 int dynmm_ml_partition(const float* weight, int K, int B, int* order, int* inv, int* counts, void* stream);
 
+/* ---- modality-level DynMM on CMU-MOSEI features (ModalityDynMM/affect/affect_dyn.py), csrc/affect_eval.hip ---- */
+/* Supervised_Learning.single_test, task "posneg-classification", accumulated over an evaluation pass (one launch per batch):
+ * counts [4] (int64) += the 2x2 table of (out[b * out_stride] >= 0, y[b] >= 0) at index 2 * pred + truth (n00, n01, n10, n11);
+ * loss_acc[0] (fp64, NULL allowed) += form 0: B * sum_b |out_b - y_b|  (L1Loss(reduction='sum') times len(batch));
+ *                                     form 1: (sum_b |out_b - y_b| / B + lossw * aux[0]) * B  (train's validation objective;
+ *                                     aux NULL: 0). */
+int dynmm_posneg_counts(const float* out, int out_stride, const float* y, int B, const float* aux, double lossw, int form,
+                        long long* counts, double* loss_acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
