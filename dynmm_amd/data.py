@@ -1,12 +1,25 @@
-"""Minimal data side for the drivers.  The reference's NYUv2 pipeline (FusionDynMM/src/datasets,
-src/preprocessing.py: cv2/torchvision host code) is out of scope; the drivers
-accept any iterable of dict batches with the reference's keys
+"""Data side of the drivers.  They accept any iterable of dict batches with the reference's keys
     'image' [N,3,H,W] f32, 'depth' [N,1,H,W] f32, 'label' [N,H,W] (0 = void),
     'label_down' {8: ..., 16: ..., 32: ...}, optionally 'label_orig'
-and ship a deterministic synthetic NYUv2-shaped source for smoke runs and benchmarks."""
+and ship two sources:
+  * NYUv2: the reference's data set (FusionDynMM/src/datasets/nyuv2) read from the layout its prepare_dataset.py writes, decoded
+    once and kept on the device; each batch's inputs come from one kernel (csrc/rgbd_aug.hip) that restates
+    src/preprocessing.py (RandomRescale, RandomCrop, RandomHSV, RandomFlip, Normalize, MultiScaleLabel for train; Rescale +
+    Normalize for test) with per-sample random choices drawn on the host.  prepare_data() builds the (train, valid) pair of
+    src/prepare_data.py;
+  * SyntheticRGBD: a deterministic synthetic NYUv2-shaped source for smoke runs and benchmarks."""
+import os
+
+import numpy as np
 import torch
 
-from . import synth
+from . import dp, synth
+
+DEPTH_MEAN = 2841.94941272766           # src/datasets/nyuv2/pytorch_dataset.py:53-58: the refined-depth statistics, used for
+DEPTH_STD = 1417.2594281672277          # both depth modes
+# one int32 row per output sample of csrc/rgbd_aug.hip: stored index, size after RandomRescale, mode (0 = crop, 1 = the
+# rescale-instead-of-crop branch), crop offsets, flip
+AUG_FIELDS = ('src', 'th', 'tw', 'mode', 'ci', 'cj', 'flip', 'pad')
 
 
 class SyntheticRGBD:
@@ -69,3 +82,216 @@ class SyntheticRGBD:
 
     def compute_class_weights(self, weight_mode='median_frequency', c=1.02):
         return self.weights_from_counts(*self.class_counts(), weight_mode=weight_mode, c=c)
+
+
+def _png_reader():
+    """cv2.imread(IMREAD_UNCHANGED) + BGR->RGB as src/datasets/nyuv2/pytorch_dataset.py:112-120 does when cv2 is importable,
+    else PIL; 16-bit grayscale PNGs come back as exact uint16 either way."""
+    try:
+        import cv2
+    except ImportError:
+        cv2 = None
+    if cv2 is not None:
+        def read(path):
+            im = cv2.imread(path, cv2.IMREAD_UNCHANGED)
+            if im is None:
+                raise OSError(f'cannot read {path}')
+            return cv2.cvtColor(im, cv2.COLOR_BGR2RGB) if im.ndim == 3 else im
+        return read
+    try:
+        from PIL import Image
+    except ImportError:
+        raise ImportError('reading NYUv2 needs cv2 or PIL (Pillow) to decode its PNG files; neither is importable') from None
+
+    def read(path):
+        with Image.open(path) as im:
+            if im.mode in ('I;16', 'I;16L', 'I;16B', 'I;16N'):
+                return np.array(im, dtype=np.uint16)
+            if im.mode == 'I':                                  # older Pillow widens 16-bit grayscale to int32
+                a = np.asarray(im)
+                if a.min() < 0 or a.max() > 65535:
+                    raise ValueError(f'{path}: values outside uint16')
+                return a.astype(np.uint16)
+            if im.mode in ('RGB', 'L', 'P'):
+                return np.array(im)
+            if im.mode == 'RGBA':
+                return np.array(im.convert('RGB'))
+            raise ValueError(f'{path}: unsupported PNG mode {im.mode}')
+    return read
+
+
+class NYUv2:
+    """One split of NYUv2 (40 classes) in the layout of src/datasets/nyuv2/prepare_dataset.py:
+        DIR/{train,test}.txt                 file lists
+        DIR/{split}/rgb/NAME.png             8-bit RGB
+        DIR/{split}/depth/NAME.png           16-bit depth in mm (depth_raw/ under depth_mode='raw')
+        DIR/{split}/labels_40/NAME.png       8-bit labels, 0 = void
+    decoded once into device tensors (rgb [S,H0,W0,3] uint8, depth [S,H0,W0] int16 holding the uint16 values, label
+    [S,H0,W0] uint8).  Iterating yields the batches DataLoader(Dataset, preprocessor) yields in src/prepare_data.py: the train
+    split shuffled with drop_last, each sample through the reference's random augmentation; the test split in order, resized to
+    height x width when stored at another size, with 'label_orig' (the stored label).  Labels are uint8.
+
+    Random choices (src/preprocessing.py:82-161) come from numpy.random.default_rng((seed, epoch)): the same on every rank, which
+    then takes its slice [rank * batch_size, (rank + 1) * batch_size) of every global batch of batch_size * world samples."""
+    n_classes_without_void = 40
+    cameras = ['kv1']
+    depth_mean, depth_std = DEPTH_MEAN, DEPTH_STD
+    weights_from_counts = staticmethod(SyntheticRGBD.weights_from_counts)
+
+    def __init__(self, data_dir, split='train', depth_mode='refined', batch_size=8, height=480, width=640,
+                 aug_scale=(1.0, 1.4), device='cuda', seed=0, rank=0, world=1):
+        if split not in ('train', 'test'):
+            raise ValueError(f'NYUv2 split must be train or test, got {split!r}')
+        if depth_mode not in ('refined', 'raw'):
+            raise ValueError(f'depth_mode must be refined or raw, got {depth_mode!r}')
+        if not os.path.isdir(data_dir):
+            raise FileNotFoundError(f'NYUv2 directory {data_dir!r} does not exist')
+        self.data_dir, self.split, self.depth_mode = data_dir, split, depth_mode
+        self.bs, self.h, self.w = batch_size, height, width
+        self.scale_low, self.scale_high = min(aug_scale), max(aug_scale)
+        self.seed, self.rank, self.world, self.device = seed, rank, world, torch.device(device)
+        self.epoch = 0
+        with open(os.path.join(data_dir, f'{split}.txt')) as f:
+            self.filenames = [ln.strip() for ln in f if ln.strip()]
+        if not self.filenames:
+            raise ValueError(f'{split}.txt lists no files')
+        rgb, depth, label = self._decode()
+        self.n = len(self.filenames)
+        self.h0, self.w0 = label.shape[1:]
+        lo, hi = dp.shard_batch(self.n, rank, world)
+        self._counts = self._histograms(label[lo:hi])
+        self.rgb = torch.from_numpy(rgb).to(self.device)
+        self.depth = torch.from_numpy(depth.view(np.int16)).to(self.device)
+        self.label = torch.from_numpy(label).to(self.device)
+        if split == 'test':
+            self._test_params = None
+
+    def _decode(self):
+        read = _png_reader()
+        ddir = 'depth_raw' if self.depth_mode == 'raw' else 'depth'
+        rgb = depth = label = None
+        for k, name in enumerate(self.filenames):
+            def path(sub):
+                return os.path.join(self.data_dir, self.split, sub, f'{name}.png')
+            im, d, lab = read(path('rgb')), read(path(ddir)), read(path('labels_40'))
+            if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+                raise ValueError(f'{path("rgb")}: expected 8-bit RGB, got {im.dtype} {im.shape}')
+            if d.dtype != np.uint16 or d.ndim != 2:
+                raise ValueError(f'{path(ddir)}: expected 16-bit single-channel depth, got {d.dtype} {d.shape}')
+            if lab.dtype != np.uint8 or lab.ndim != 2:
+                raise ValueError(f'{path("labels_40")}: expected 8-bit single-channel labels, got {lab.dtype} {lab.shape}')
+            if rgb is None:
+                n, (h0, w0) = len(self.filenames), lab.shape
+                rgb = np.empty((n, h0, w0, 3), np.uint8)
+                depth = np.empty((n, h0, w0), np.uint16)
+                label = np.empty((n, h0, w0), np.uint8)
+            if im.shape[:2] != label.shape[1:] or d.shape != label.shape[1:] or lab.shape != label.shape[1:]:
+                raise ValueError(f'{name}: every image of the {self.split} split must have the size of the first, '
+                                 f'{label.shape[1:]} (got rgb {im.shape[:2]}, depth {d.shape}, label {lab.shape})')
+            if lab.max() > self.n_classes_without_void:
+                raise ValueError(f'{path("labels_40")}: label {lab.max()} > {self.n_classes_without_void}')
+            rgb[k], depth[k], label[k] = im, d, lab
+        return rgb, depth, label
+
+    def _histograms(self, labels):
+        n_cls = self.n_classes_without_void + 1
+        per_class, with_class = np.zeros(n_cls), np.zeros(n_cls)
+        for lab in labels:
+            dist = np.bincount(lab.reshape(-1), minlength=n_cls)
+            per_class += dist
+            with_class += (dist > 0) * lab.size
+        return per_class, with_class
+
+    def class_counts(self):
+        """(pixels per class, pixels of the images containing the class), void at index 0, over this rank's contiguous shard
+        of the stored labels (src/datasets/dataset_base.py:160-186): summed over the ranks they are the whole split's."""
+        return self._counts[0].copy(), self._counts[1].copy()
+
+    def compute_class_weights(self, weight_mode='median_frequency', c=1.02):
+        return self.weights_from_counts(*self.class_counts(), weight_mode=weight_mode, c=c)
+
+    def set_epoch(self, epoch):
+        """the shuffle and the augmentation of the next iteration are those of `epoch` (resumed runs)"""
+        self.epoch = epoch
+
+    def __len__(self):
+        if self.split == 'train':
+            return self.n // (self.bs * self.world)
+        return (self.n + self.bs - 1) // self.bs
+
+    def sample_params(self, epoch):
+        """This rank's batches of `epoch`: (params int32 [n_batches, batch_size, 8] (AUG_FIELDS), hsv float32
+        [n_batches, batch_size, 4]) for train; (params [n_samples, 8], None) for test."""
+        if self.split == 'test':
+            mode = 0 if (self.h0, self.w0) == (self.h, self.w) else 1       # Rescale only when the size differs
+            p = np.zeros((self.n, 8), np.int32)
+            p[:, 0], p[:, 1], p[:, 2], p[:, 3] = np.arange(self.n), self.h0, self.w0, mode
+            return p, None
+        gb = self.bs * self.world
+        nb = self.n // gb
+        rng = np.random.default_rng((self.seed, epoch))
+        order = rng.permutation(self.n)[:nb * gb]
+        p, hsv = draw_augmentation(rng, len(order), self.h0, self.w0, self.h, self.w, self.scale_low, self.scale_high)
+        p[:, 0] = order
+        lo = self.rank * self.bs
+        p = p.reshape(nb, gb, 8)[:, lo:lo + self.bs]
+        hsv = hsv.reshape(nb, gb, 4)[:, lo:lo + self.bs]
+        return np.ascontiguousarray(p), np.ascontiguousarray(hsv)
+
+    def __iter__(self):
+        from . import ops
+        raw = self.depth_mode == 'raw'
+        if self.split == 'test':
+            if self._test_params is None:
+                self._test_params = torch.from_numpy(self.sample_params(0)[0]).to(self.device)
+            for b0 in range(0, self.n, self.bs):
+                b1 = min(b0 + self.bs, self.n)
+                image, depth, label, down = ops.rgbd_aug(self.rgb, self.depth, self.label, self._test_params[b0:b1], self.h,
+                                                         self.w, self.depth_mean, self.depth_std, raw)
+                yield {'image': image, 'depth': depth, 'label': label, 'label_down': down, 'label_orig': self.label[b0:b1]}
+            return
+        p, hsv = self.sample_params(self.epoch)
+        self.epoch += 1
+        p, hsv = torch.from_numpy(p).to(self.device), torch.from_numpy(hsv).to(self.device)   # one upload per epoch
+        for b in range(p.shape[0]):
+            image, depth, label, down = ops.rgbd_aug(self.rgb, self.depth, self.label, p[b], self.h, self.w, self.depth_mean,
+                                                     self.depth_std, raw, hsv=hsv[b])
+            yield {'image': image, 'depth': depth, 'label': label, 'label_down': down}
+
+
+def draw_augmentation(rng, n, h0, w0, height, width, scale_low=1.0, scale_high=1.4):
+    """n samples' random choices of src/preprocessing.py's train transforms (the stored index left at 0): params int32 [n, 8]
+    (AUG_FIELDS), hsv float32 [n, 4].  RandomRescale s ~ U(low, high), th = round(s * h0), tw = round(s * w0) (:82-106);
+    RandomCrop's offsets i in [0, th - height), j in [0, tw - width), or, when th <= height or tw <= width, the second resize to
+    height x width (mode 1, :109-131); RandomHSV h, s ~ U(0.9, 1.1), v ~ U(-25, 25) (:134-161); RandomFlip when rand > 0.5."""
+    s = rng.uniform(scale_low, scale_high, n)
+    th, tw = np.rint(s * h0).astype(np.int64), np.rint(s * w0).astype(np.int64)
+    rescale = (th <= height) | (tw <= width)
+    ci = np.where(rescale, 0, rng.integers(0, np.maximum(th - height, 1)))
+    cj = np.where(rescale, 0, rng.integers(0, np.maximum(tw - width, 1)))
+    hsv = np.zeros((n, 4), np.float32)
+    hsv[:, 0] = rng.uniform(0.9, 1.1, n)
+    hsv[:, 1] = rng.uniform(0.9, 1.1, n)
+    hsv[:, 2] = rng.uniform(-25, 25, n)
+    flip = rng.random(n) > 0.5
+    p = np.zeros((n, 8), np.int32)
+    p[:, 1], p[:, 2], p[:, 3], p[:, 4], p[:, 5], p[:, 6] = th, tw, rescale, ci, cj, flip
+    return p, hsv
+
+
+def nyuv2_split(args, split, device, rank=0, world=1, seed=0):
+    bs = args.batch_size if split == 'train' else (args.batch_size_valid or args.batch_size)
+    return NYUv2(args.dataset_dir, split, 'raw' if args.raw_depth else 'refined', bs, args.height, args.width,
+                 aug_scale=(args.aug_scale_min, args.aug_scale_max), device=device, seed=seed, rank=rank, world=world)
+
+
+def prepare_data(args, device, rank=0, world=1, seed=0):
+    """src/prepare_data.py:18-163 for --dataset nyuv2: (train, valid) with valid = the test split (batch_size_valid or
+    batch_size, in order).  Under data parallel each rank gets its slice of every global training batch; the valid set is whole
+    on every rank (engine.evaluate shards its batches)."""
+    if args.dataset != 'nyuv2':
+        raise NotImplementedError(f'--dataset {args.dataset}: only nyuv2 has a reader (dynmm_amd.data.NYUv2)')
+    if args.dataset_dir is None:
+        raise NotImplementedError('--dataset nyuv2 needs --dataset_dir (the layout of '
+                                  'src/datasets/nyuv2/prepare_dataset.py)')
+    return (nyuv2_split(args, 'train', device, rank, world, seed), nyuv2_split(args, 'test', device, rank, world, seed))

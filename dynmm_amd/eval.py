@@ -1,7 +1,8 @@
-"""python -m dynmm_amd.eval --dynamic --global-gate [--baseline] --hard --ckpt_path CKPT ...
+"""python -m dynmm_amd.eval --dynamic --global-gate [--baseline] --hard --ckpt_path CKPT --dataset nyuv2 --dataset_dir DIR ...
 
 Counterpart of FusionDynMM/eval.py:35-151: load a (reference-format) checkpoint strictly, set the gate
-flags, optional Gaussian-noise robustness runs (modes 0/1/2), mIoU*100 per run."""
+flags, optional Gaussian-noise robustness runs (modes 0/1/2), mIoU*100 per run.  With --dataset_dir the NYUv2 test split is
+evaluated (dynmm_amd.data.NYUv2); without one, a synthetic NYUv2-shaped set; other data sets have no reader and are refused."""
 import random
 import sys
 
@@ -9,7 +10,7 @@ import numpy as np
 import torch
 
 from . import engine
-from .data import SyntheticRGBD
+from .data import SyntheticRGBD, nyuv2_split
 from .src.args import ArgumentParserRGBDSegmentation
 from .src.build_model import build_model
 
@@ -24,8 +25,8 @@ def set_seed(seed):
 def run(args, model, valid_loader, device=None, use_graph=True):
     """eval.py:63-151 for a model the caller built and ANY loader the caller brings — an iterable of dicts with `image` [N,3,H,W],
     `depth` [N,1,H,W] (normalised as src/preprocessing.py does) and `label_orig` [N,H0,W0] (0 = void), on the host or the device:
-    the entry a user with NYUv2 on disk calls (`python -m dynmm_amd.eval` itself ships only the synthetic loader; the data set's
-    preparation is host-side code outside the hot path).  Sets the gate flags from `args` (hard / ini / baseline), runs
+    the entry `python -m dynmm_amd.eval` calls with the NYUv2 test split (dynmm_amd.data.NYUv2) or the synthetic set, and the one
+    a user with another loader calls.  Sets the gate flags from `args` (hard / ini / baseline), runs
     `args.num_runs` passes with the reference's per-run seeds and Gaussian-noise modes 0 / 1 / 2, prints and returns mIoU*100 per
     run.  `use_graph`: the forward is replayed as hipGraphs (engine.InferStep; eager where that does not apply)."""
     device = next(model.parameters()).device if device is None else device
@@ -64,13 +65,18 @@ def main(argv=None):
     p.add_argument('--no_hip_graph', action='store_true', help='eager launches instead of hipGraph replays of the forward')
     args = p.parse_args(argv)
     args.pretrained_on_imagenet = False
+    if args.dataset_dir is not None and args.dataset not in ('nyuv2', 'synthetic'):
+        raise NotImplementedError(f'--dataset {args.dataset}: only nyuv2 (and synthetic) have a reader on the HIP path')
     model, device = build_model(args, n_classes=40)
     if args.ckpt_path:
         ckpt = torch.load(args.ckpt_path, map_location=device)
         model.load_state_dict(ckpt['state_dict'])               # strict, eval.py:60-61
         print(f'Loaded checkpoint from {args.ckpt_path}')
-    data = SyntheticRGBD(args.synthetic_samples, args.batch_size_valid or args.batch_size, args.height, args.width,
-                         seed=77, device=device)
+    if args.dataset_dir is not None and args.dataset == 'nyuv2':
+        data = nyuv2_split(args, 'test', device)
+    else:
+        data = SyntheticRGBD(args.synthetic_samples, args.batch_size_valid or args.batch_size, args.height, args.width,
+                             seed=77, device=device)
     return run(args, model, data, device, use_graph=not args.no_hip_graph)
 
 

@@ -166,6 +166,7 @@ SIGNATURES = {
     'dynmm_ml_counts': (c_i, [c_f, c_f, c_i, c_i, c_f, c_f, c_f]),
     'dynmm_ml_partition': (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f]),
     'dynmm_posneg_counts': (c_i, [c_f, c_i, c_f, c_i, c_f, C.c_double, c_i, c_f, c_f, c_f]),
+    'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 
 ABI_VERSION = 4

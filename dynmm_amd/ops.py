@@ -2218,3 +2218,37 @@ def eval_confusion(logits, label, cm):
     L.check(lib.dynmm_eval_confusion(_p(logits), lab.data_ptr(), cm.data_ptr(), N, Cc, H, W, Ho, Wo, _stream()),
             'eval_confusion')
     return cm
+
+
+def rgbd_aug(rgb, depth, label, params, H, W, depth_mean, depth_std, raw_depth=False, hsv=None, label_down=True):
+    """One batch of network inputs from a decoded split held on the device (csrc/rgbd_aug.hip; dynmm_amd/data.py NYUv2):
+    rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit (int16 storage of the uint16 millimetres), label [S,H0,W0] uint8;
+    params [N,8] int32 (data.AUG_FIELDS) picks and maps each output sample, hsv [N,4] float32 the RandomHSV factors (None: the
+    test split's normalise-only path).  Returns image [N,3,H,W] f32, depth [N,1,H,W] f32, label [N,H,W] uint8 and the label
+    pyramid {8, 16, 32: [N,H/r,W/r] uint8} (None without `label_down`)."""
+    lib = _lib()
+    for t, name, dt in ((rgb, 'rgb', torch.uint8), (depth, 'depth', torch.int16), (label, 'label', torch.uint8),
+                        (params, 'params', torch.int32)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise L.DynmmHipError(f'rgbd_aug: {name} must be a contiguous {dt} tensor on a HIP device')
+    S, H0, W0, _ = rgb.shape
+    if tuple(depth.shape) != (S, H0, W0) or tuple(label.shape) != (S, H0, W0) or rgb.shape[-1] != 3:
+        raise L.DynmmHipError(f'rgbd_aug: rgb {tuple(rgb.shape)}, depth {tuple(depth.shape)}, label {tuple(label.shape)}')
+    N = params.shape[0]
+    if params.dim() != 2 or params.shape[1] != 8:
+        raise L.DynmmHipError(f'rgbd_aug: params must be [N, 8], got {tuple(params.shape)}')
+    if hsv is not None and (not hsv.is_cuda or hsv.dtype != torch.float32 or tuple(hsv.shape) != (N, 4)
+                            or not hsv.is_contiguous()):
+        raise L.DynmmHipError('rgbd_aug: hsv must be a contiguous float32 [N, 4] tensor on the device')
+    if W % 4 != 0:
+        raise L.DynmmHipError(f'rgbd_aug: width {W} must be a multiple of 4')
+    dev = rgb.device
+    image = torch.empty(N, 3, H, W, device=dev)
+    depth_out = torch.empty(N, 1, H, W, device=dev)
+    lab = torch.empty(N, H, W, device=dev, dtype=torch.uint8)
+    down = {r: torch.empty(N, H // r, W // r, device=dev, dtype=torch.uint8) for r in (8, 16, 32)} if label_down else None
+    L.check(lib.dynmm_rgbd_aug(rgb.data_ptr(), depth.data_ptr(), label.data_ptr(), S, H0, W0, params.data_ptr(), _p(hsv), N,
+                               H, W, float(depth_mean), float(depth_std), int(bool(raw_depth)), image.data_ptr(),
+                               depth_out.data_ptr(), lab.data_ptr(), *((down[r].data_ptr() for r in (8, 16, 32)) if down
+                                                                      else (None, None, None)), _stream()), 'rgbd_aug')
+    return image, depth_out, lab, down

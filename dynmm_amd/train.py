@@ -1,10 +1,12 @@
 """python -m dynmm_amd.train --dynamic --global-gate --encoder resnet34 --encoder_block NonBottleneck1D \
-       --decoder_channels_mode constant --dataset synthetic [...]
+       --decoder_channels_mode constant --dataset nyuv2 --dataset_dir DIR [...]     (or --dataset synthetic)
 
 Counterpart of FusionDynMM/train.py on the HIP path: same flags (dynmm_amd/src/args.py), same epoch
 protocol (ini_stage / hard_gate / temperature per epoch, OneCycle stepped per epoch, lr scaled by
 batch/8, total loss rule, NaN guard, periodic validation, checkpoints with the reference's keys).
-One process per GPU under torch.distributed.run = data parallel (new; the reference is single-GPU)."""
+One process per GPU under torch.distributed.run = data parallel (new; the reference is single-GPU).
+Data: --dataset nyuv2 --dataset_dir DIR trains on NYUv2 through dynmm_amd.data.prepare_data (decoded once onto the device, one
+augmentation kernel per batch); --dataset synthetic on SyntheticRGBD; the other data sets have no reader and are refused."""
 import json
 import os
 import sys
@@ -15,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from . import dp, engine, schedules
-from .data import SyntheticRGBD
+from .data import SyntheticRGBD, prepare_data
 from .src.args import ArgumentParserRGBDSegmentation
 from .src.build_model import build_model
 from .src.pretrained import load_ckpt
@@ -26,6 +28,7 @@ def parse_args(argv=None):
     p.set_common_args()
     p.add_argument('--synthetic_samples', type=int, default=64)
     p.add_argument('--hip_graph', action='store_true', help='replay each step as one hipGraph')
+    p.add_argument('--data_seed', type=int, default=0, help='seed of the NYUv2 shuffle and augmentation')
     args = p.parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     args.lr = schedules.scaled_lr(args.lr, args.batch_size * world)      # train.py:46-49 on the GLOBAL batch
@@ -52,12 +55,17 @@ def train_main(argv=None):
         raise NotImplementedError('only --dataset synthetic ships with the HIP path; pass your own loader to '
                                   'dynmm_amd.train.run(...) for real data (NYUv2 preparation is host-side code '
                                   'outside the hot path)')
+    if args.dataset not in ('synthetic', 'nyuv2'):
+        raise NotImplementedError(f'--dataset {args.dataset}: only nyuv2 (and synthetic) have a reader on the HIP path')
     ckpt_dir = os.path.join(args.results_dir, args.dataset, time.strftime('checkpoints_%d_%m_%Y-%H_%M_%S'))
     if rank == 0:
         os.makedirs(ckpt_dir, exist_ok=True)
         with open(os.path.join(ckpt_dir, 'args.json'), 'w') as f:
             json.dump(vars(args), f, sort_keys=True, indent=4)
     model, device = build_model(args, n_classes=40)
+    if args.dataset == 'nyuv2':
+        train, valid = prepare_data(args, device, rank, world, seed=args.data_seed)
+        return run(args, model, train, valid, ckpt_dir, rank, world)
     lo, hi = dp.shard_batch(args.synthetic_samples, rank, world)
     train = SyntheticRGBD(hi - lo, args.batch_size, args.height, args.width, seed=1000 * rank, device=device, nyu_like=False)
     valid = SyntheticRGBD(max(args.batch_size, 8), args.batch_size_valid or args.batch_size, args.height, args.width,
@@ -112,6 +120,8 @@ def run(args, model, train_loader, valid_loader, ckpt_dir, rank=0, world=1):
         # OneCycleLR(cycle_momentum=True) also rewrites the momentum (SGD) / beta1 (Adam) every epoch
         step.opt.set_momentum(schedules.one_cycle_momentum(epoch, args.epochs))
         model.train()
+        if hasattr(train_loader, 'set_epoch'):            # reshuffle per epoch, reproducibly across a resume
+            train_loader.set_epoch(epoch)
         t0, tot, flop, nb = time.time(), [], [], 0
         for i, sample in enumerate(train_loader):
             targets = [sample['label']] + [sample['label_down'][r] for r in (8, 16, 32)]

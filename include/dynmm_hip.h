@@ -626,6 +626,19 @@ int dynmm_ml_partition(const float* weight, int K, int B, int* order, int* inv, 
 int dynmm_posneg_counts(const float* out, int out_stride, const float* y, int B, const float* aux, double lossw, int form,
                         long long* counts, double* loss_acc, void* stream);
 
+/* ---- NYUv2 input pipeline (FusionDynMM/src/preprocessing.py), csrc/rgbd_aug.hip ---- */
+/* One batch of network inputs from decoded samples kept on the device: rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit,
+ * label [S,H0,W0] uint8.  params [N,8] int32 per output sample: {stored index, th, tw, mode, ci, cj, flip, 0}: the stored sample
+ * is resized (cv2 INTER_LINEAR image, INTER_NEAREST depth / label) to th x tw, then cropped at (ci, cj) (mode 0) or resized
+ * again to H x W (mode 1), then flipped.  hsv [N,4] float32 {h, s, v, 0} applies RandomHSV (NULL: the test split, no jitter).
+ * Outputs: image [N,3,H,W] (/255, ImageNet mean / std), depth_out [N,1,H,W] ((d - depth_mean) / depth_std; raw_depth keeps
+ * zeros at 0), label_out [N,H,W] uint8, and optionally (all three or none) the label pyramid down8/16/32 [N,H/r,W/r] uint8
+ * (cv2 INTER_NEAREST of label_out).  W % 4 == 0; image / depth_out / params 16-byte and label_out 4-byte aligned. */
+int dynmm_rgbd_aug(const unsigned char* rgb, const unsigned short* depth, const unsigned char* label, int S, int H0, int W0,
+                   const int* params, const float* hsv, int N, int H, int W, float depth_mean, float depth_std, int raw_depth,
+                   float* image, float* depth_out, unsigned char* label_out, unsigned char* down8, unsigned char* down16,
+                   unsigned char* down32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
