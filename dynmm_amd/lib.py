@@ -14,6 +14,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 DYNMM_OK, DYNMM_EINVAL, DYNMM_EUNSUPPORTED, DYNMM_EWORKSPACE = 0, -1, -2, -3
 ACT = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2}
+LOSS_BCE_LOGITS, LOSS_L1 = 0, 1          # dynmm_head_loss kinds
 
 c_f = C.c_void_p       # device pointers travel as void* (tensor.data_ptr() or None)
 c_i = C.c_int
@@ -166,6 +167,7 @@ SIGNATURES = {
     'dynmm_ml_counts': (c_i, [c_f, c_f, c_i, c_i, c_f, c_f, c_f]),
     'dynmm_ml_partition': (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f]),
     'dynmm_posneg_counts': (c_i, [c_f, c_i, c_f, c_i, c_f, C.c_double, c_i, c_f, c_f, c_f]),
+    'dynmm_head_loss': (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 

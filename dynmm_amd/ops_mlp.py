@@ -188,6 +188,35 @@ def ml_loss_backward(logits, preds, target, temp, hard, reg):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# single-expert objective (Step I: one model, no gate)
+# ---------------------------------------------------------------------------------------------------------------
+HEAD_LOSSES = {'bce': L.LOSS_BCE_LOGITS, 'l1': L.LOSS_L1}
+
+
+def head_loss(out, target, kind, seed=True, loss_acc=None):
+    """(loss [1], d_out [B,C] or None): BCEWithLogitsLoss() ('bce') or L1Loss() ('l1') of out [B,C] (or [B]) against target of
+    the same number of elements, the mean over all of them, and the backward seed dloss/dout — one launch
+    (csrc/expert_loss.hip).  loss_acc: optional fp64 device [1] that receives += loss * B (an epoch's training loss)."""
+    if kind not in HEAD_LOSSES:
+        raise ValueError(f'head_loss: kind must be one of {sorted(HEAD_LOSSES)}, got {kind!r}')
+    o = _chk(out.detach(), 'out')
+    B = o.shape[0]
+    Cc = o.numel() // max(B, 1)
+    tgt = _chk(target.detach().float(), 'target')
+    if o.dim() not in (1, 2) or o.numel() == 0 or tgt.numel() != o.numel():
+        raise L.DynmmHipError(f'head_loss: out must be [B] or [B, C] and target hold as many values, got out {tuple(o.shape)}, '
+                              f'target {tuple(tgt.shape)}')
+    if loss_acc is not None and not (loss_acc.is_cuda and loss_acc.dtype == torch.float64 and loss_acc.numel() >= 1):
+        raise L.DynmmHipError('head_loss: loss_acc must be an fp64 device tensor')
+    f32 = dict(device=o.device, dtype=torch.float32)
+    loss = torch.empty(1, **f32)
+    d_out = torch.empty(o.shape, **f32) if seed else None
+    L.check(_lib().dynmm_head_loss(_p(o), _p(tgt), B, Cc, HEAD_LOSSES[kind], _p(loss), _p(d_out),
+                                   None if loss_acc is None else loss_acc.data_ptr(), _stream()), 'head_loss')
+    return loss, d_out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # evaluation: per-class counts on the device, F1 on the host from one read
 # ---------------------------------------------------------------------------------------------------------------
 class MultilabelCounts:

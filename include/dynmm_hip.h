@@ -35,6 +35,9 @@ extern "C" {
 #define DYNMM_ACT_RELU 1
 #define DYNMM_ACT_TANH 2
 
+#define DYNMM_LOSS_BCE_LOGITS 0   /* dynmm_head_loss kinds */
+#define DYNMM_LOSS_L1 1
+
 /* ABI version + build info (smoke / loader check). */
 int dynmm_abi_version(void);
 const char* dynmm_build_info(void);
@@ -625,6 +628,14 @@ int dynmm_ml_partition(const float* weight, int K, int B, int* order, int* inv, 
  *                                     aux NULL: 0). */
 int dynmm_posneg_counts(const float* out, int out_stride, const float* y, int B, const float* aux, double lossw, int form,
                         long long* counts, double* loss_acc, void* stream);
+
+/* ---- one expert trained on its own (modality-level DynMM, Step I), csrc/expert_loss.hip ---- */
+/* Objective of a single head out [B,C] against target [B,C], no gate: kind DYNMM_LOSS_BCE_LOGITS (BCEWithLogitsLoss, torch's
+ * stable form) or DYNMM_LOSS_L1 (L1Loss), both the mean over B*C.  loss[0] = that mean (the slot the optimizer's non-finite
+ * guard reads); d_out [B,C] (NULL allowed) = dloss/dout, the backward seed; loss_acc[0] (fp64, NULL allowed) += loss * B.
+ * One workgroup, fixed summation order (deterministic). */
+int dynmm_head_loss(const float* out, const float* target, int B, int C, int kind, float* loss, float* d_out,
+                    double* loss_acc, void* stream);
 
 /* ---- NYUv2 input pipeline (FusionDynMM/src/preprocessing.py), csrc/rgbd_aug.hip ---- */
 /* One batch of network inputs from decoded samples kept on the device: rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit,
