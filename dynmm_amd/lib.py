@@ -103,6 +103,12 @@ SIGNATURES = {
     'dynmm_upsample2x_dw3x3_fwd': (c_i, [c_f] * 5 + [c_i] * 4 + [c_f]),
     'dynmm_upsample2x_dw3x3_bwd_workspace_bytes': (c_sz, [c_i, c_i]),
     'dynmm_upsample2x_dw3x3_bwd': (c_i, [c_f] * 7 + [c_i] * 4 + [c_f]),
+    'dynmm_upsample2x_fwd': (c_i, [c_f] * 3 + [c_i] * 5 + [c_f]),
+    'dynmm_upsample2x_bwd': (c_i, [c_f] * 2 + [c_i] * 5 + [c_f]),
+    'dynmm_upsample2x_dw3x3_rep_fwd': (c_i, [c_f] * 5 + [c_i] * 4 + [c_f]),
+    'dynmm_upsample2x_dw3x3_rep_bwd': (c_i, [c_f] * 7 + [c_i] * 4 + [c_f]),
+    'dynmm_bilinear_into_fwd': (c_i, [c_f, c_f] + [c_i] * 8 + [c_f]),
+    'dynmm_bilinear_into_bwd': (c_i, [c_f, c_f] + [c_i] * 8 + [c_f]),
     'dynmm_gap2_fwd': (c_i, [c_f] * 4 + [c_i, c_i, c_f]),
     'dynmm_se_coeff_fwd': (c_i, [c_f, c_f, _PP, c_f, c_i] + [c_f] * 6 + [c_i, c_i, c_i, c_f]),
     'dynmm_se_coeff_bwd_workspace_bytes': (c_sz, [c_i, c_i]),

@@ -1,5 +1,5 @@
 """ESANet decoder (model.py:244-410): 3 x [ConvBNAct 3x3, n x NonBottleneck1D, side output (train),
-learned 2x upsample + skip add], 3x3 classifier, two learned 2x upsamples."""
+2x upsample (+ skip add with encoder_decoder_fusion='add')], 3x3 classifier, two 2x upsamples."""
 import torch
 import torch.nn as nn
 
@@ -7,28 +7,50 @@ from .. import ops
 from .blocks import ConvBNAct, NonBottleneck1D, chain_ok
 
 
-class Upsample(nn.Module):
-    """'learned-3x3-zeropad': nearest x2 + depthwise 3x3 initialised to mimic bilinear (model.py:385-395)."""
+UPSAMPLING_MODES = ('nearest', 'bilinear', 'learned-3x3', 'learned-3x3-zeropad')
 
-    def __init__(self, channels):
+
+class Upsample(nn.Module):
+    """Upsample(mode, channels) (model.py:360-410): x2 'nearest' / 'bilinear' (align_corners=False, no parameters: the
+    reference's pad and conv are nn.Identity), or the learned modes — nearest x2 + depthwise 3x3 initialised to mimic
+    bilinear (model.py:385-395), with zero borders ('learned-3x3-zeropad', conv padding 1) or replicated ones
+    ('learned-3x3': ReplicationPad2d(1) + conv padding 0).  forward(x, skip) also adds the decoder's skip connection."""
+
+    def __init__(self, mode='learned-3x3-zeropad', channels=None):
         super().__init__()
-        self.conv = nn.Conv2d(channels, channels, 3, padding=1, groups=channels)
-        k = torch.tensor([1., 2., 1.]) / 4
-        with torch.no_grad():
-            self.conv.weight.copy_((k[:, None] * k[None, :]).expand(channels, 1, 3, 3))
-            self.conv.bias.zero_()
+        if mode not in UPSAMPLING_MODES:
+            raise NotImplementedError(f'Upsampling mode must be one of {UPSAMPLING_MODES}. Got {mode}')
+        self.mode = mode
+        if 'learned-3x3' in mode:
+            self.pad = nn.Identity()          # (ReplicationPad2d for 'learned-3x3' has no state; the kernel clamps)
+            self.conv = nn.Conv2d(channels, channels, 3, padding=1 if mode == 'learned-3x3-zeropad' else 0,
+                                  groups=channels)
+            k = torch.tensor([1., 2., 1.]) / 4
+            with torch.no_grad():
+                self.conv.weight.copy_((k[:, None] * k[None, :]).expand(channels, 1, 3, 3))
+                self.conv.bias.zero_()
+        else:
+            self.pad = nn.Identity()
+            self.conv = nn.Identity()
 
     def forward(self, x, skip=None):
-        return ops.upsample2x_dw3x3(x, self.conv.weight, self.conv.bias, skip)
+        if self.mode == 'learned-3x3-zeropad':
+            return ops.upsample2x_dw3x3(x, self.conv.weight, self.conv.bias, skip)
+        if self.mode == 'learned-3x3':
+            return ops.upsample2x_dw3x3(x, self.conv.weight, self.conv.bias, skip, border='replicate')
+        return ops.upsample2x(x, self.mode, skip)
 
 
 class DecoderModule(nn.Module):
-    def __init__(self, channels_in, channels_dec, nr_decoder_blocks, num_classes):
+    def __init__(self, channels_in, channels_dec, nr_decoder_blocks, num_classes, upsampling_mode='learned-3x3-zeropad',
+                 encoder_decoder_fusion='add'):
         super().__init__()
+        self.upsampling_mode = upsampling_mode
+        self.encoder_decoder_fusion = encoder_decoder_fusion
         self.conv3x3 = ConvBNAct(channels_in, channels_dec, 3)
         self.decoder_blocks = nn.Sequential(*[NonBottleneck1D(channels_dec, channels_dec)
                                               for _ in range(nr_decoder_blocks)])
-        self.upsample = Upsample(channels_dec)
+        self.upsample = Upsample(upsampling_mode, channels_dec)
         self.side_output = nn.Conv2d(channels_dec, num_classes, 1)
 
     def forward(self, x, skip):
@@ -42,21 +64,27 @@ class DecoderModule(nn.Module):
             s = self.side_output
             y, ys = ops.fan_out(y, 2)            # y feeds the side output AND the up-sampling
             side = ops.conv2d(ys, s.weight, s.bias, 1, 0)
-        return self.upsample(y, skip), side
+        # model.py:354-355: the encoder features are added only with encoder_decoder_fusion == 'add'
+        return self.upsample(y, skip if self.encoder_decoder_fusion == 'add' else None), side
 
 
 class Decoder(nn.Module):
-    def __init__(self, channels_in, channels_decoder, nr_decoder_blocks, num_classes):
+    def __init__(self, channels_in, channels_decoder, nr_decoder_blocks, num_classes,
+                 upsampling_mode='learned-3x3-zeropad', encoder_decoder_fusion='add'):
         super().__init__()
         cd = channels_decoder
-        self.decoder_module_1 = DecoderModule(channels_in, cd[0], nr_decoder_blocks[0], num_classes)
-        self.decoder_module_2 = DecoderModule(cd[0], cd[1], nr_decoder_blocks[1], num_classes)
-        self.decoder_module_3 = DecoderModule(cd[1], cd[2], nr_decoder_blocks[2], num_classes)
+        kw = dict(upsampling_mode=upsampling_mode, encoder_decoder_fusion=encoder_decoder_fusion)
+        self.decoder_module_1 = DecoderModule(channels_in, cd[0], nr_decoder_blocks[0], num_classes, **kw)
+        self.decoder_module_2 = DecoderModule(cd[0], cd[1], nr_decoder_blocks[1], num_classes, **kw)
+        self.decoder_module_3 = DecoderModule(cd[1], cd[2], nr_decoder_blocks[2], num_classes, **kw)
         self.conv_out = nn.Conv2d(cd[2], num_classes, 3, padding=1)
-        self.upsample1 = Upsample(num_classes)
-        self.upsample2 = Upsample(num_classes)
+        self.upsample1 = Upsample(upsampling_mode, num_classes)
+        self.upsample2 = Upsample(upsampling_mode, num_classes)
+        self.upsampling_mode = upsampling_mode
         # engine.TrainStep sets this: in training the full-resolution logits feed the loss only, so the last
-        # up-sampling is fused with the cross entropy (ops.DeferredLogits, csrc/tail.hip) and never materialised
+        # up-sampling is fused with the cross entropy (ops.DeferredLogits, csrc/tail.hip) and never materialised.
+        # The fused tail restates 'learned-3x3-zeropad' only: with any other mode the logits are materialised and the
+        # loss takes the plain cross-entropy kernels (what TrainStep(fuse_tail=False) runs).
         self.defer_tail = False
 
     def forward(self, enc_outs, unpermute=None):
@@ -71,7 +99,7 @@ class Decoder(nn.Module):
         out = ops.conv2d(out, c.weight, c.bias, 1, 1)
         if unpermute is not None:
             out = ops.batch_permute(out, *unpermute)
-        if self.training and self.defer_tail and torch.is_grad_enabled():
+        if self.training and self.defer_tail and torch.is_grad_enabled() and self.upsampling_mode == 'learned-3x3-zeropad':
             out = ops.DeferredLogits(self.upsample1(out), self.upsample2.conv)
         else:
             out = self.upsample2(self.upsample1(out))

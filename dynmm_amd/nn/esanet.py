@@ -16,7 +16,7 @@ class ESANet(SkipGateESANet):
                  pretrained_dir='./trained_models/imagenet', activation='relu', encoder_decoder_fusion='add',
                  context_module='ppm', nr_decoder_blocks=None, fuse_depth_in_rgb_encoder='SE-add',
                  upsampling='bilinear'):
-        # the reference's defaults (model.py:20-35), including the ones the HIP path refuses loudly (bilinear up-sampling)
+        # the reference's defaults (model.py:20-35): bilinear up-sampling, PPM resized bilinearly, skip adds
         super().__init__(height=height, width=width, num_classes=num_classes, encoder_rgb=encoder_rgb,
                          encoder_depth=encoder_depth, encoder_block=encoder_block, channels_decoder=channels_decoder,
                          pretrained_on_imagenet=pretrained_on_imagenet, pretrained_dir=pretrained_dir,

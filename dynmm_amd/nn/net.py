@@ -16,7 +16,7 @@ import torch.nn as nn
 from .. import ops
 from .blocks import ConvBNAct, ResNetEncoder, conv_bn_act
 from .context import get_context_module
-from .decoder import Decoder
+from .decoder import UPSAMPLING_MODES, Decoder
 from .fusion import SqueezeAndExciteFusionAdd
 
 
@@ -82,6 +82,45 @@ def encoder_stage_pair(model, j, r_in, d_in):
     return r, d
 
 
+def check_decoder_options(upsampling, encoder_decoder_fusion):
+    if upsampling not in UPSAMPLING_MODES:
+        raise NotImplementedError(f'Upsampling mode must be one of {UPSAMPLING_MODES}. Got {upsampling}')
+    if encoder_decoder_fusion not in ('add', 'None'):
+        raise NotImplementedError(f'encoder_decoder_fusion must be "add" or "None". Got {encoder_decoder_fusion}')
+
+
+def build_decoder_side(model, channels_decoder, nr_decoder_blocks, num_classes, context_module, upsampling,
+                       encoder_decoder_fusion):
+    """Skip layers, context module and decoder of the three networks (…globalgate.py:145-207, model_skip_mod.py:139-199,
+    model.py:127-187).  encoder_decoder_fusion 'add': skip_layer1..3 = ConvBNAct 1x1 where the channel counts differ,
+    else an empty Sequential; 'None': skip_layer0..3 = nn.Identity and the decoder adds nothing.  The context module
+    resizes with 'nearest' for the learned up-samplings (they only double a map) and with the decoder's mode otherwise."""
+    enc = model.encoder_rgb
+    model.encoder_decoder_fusion = encoder_decoder_fusion
+    if encoder_decoder_fusion == 'add':
+        for j, (cin, cout) in enumerate(((enc.down_4_channels_out, channels_decoder[2]),
+                                         (enc.down_8_channels_out, channels_decoder[1]),
+                                         (enc.down_16_channels_out, channels_decoder[0])), start=1):
+            setattr(model, f'skip_layer{j}', nn.Sequential(*([ConvBNAct(cin, cout, 1)] if cin != cout else [])))
+    else:
+        for j in range(4):
+            setattr(model, f'skip_layer{j}', nn.Identity())
+    ctx_mode = 'nearest' if 'learned-3x3' in upsampling else upsampling
+    model.context_module, ch_ctx = get_context_module(context_module, enc.down_32_channels_out, channels_decoder[0],
+                                                      input_size=(model.height // 32, model.width // 32),
+                                                      upsampling_mode=ctx_mode)
+    model.decoder = Decoder(ch_ctx, channels_decoder, nr_decoder_blocks, num_classes, upsampling_mode=upsampling,
+                            encoder_decoder_fusion=encoder_decoder_fusion)
+
+
+def decoder_skip(model, j, fuse):
+    """What stage j's fused map hands the decoder: skip_layer{j}(fuse), or None when nothing is added."""
+    if model.encoder_decoder_fusion != 'add':
+        return None
+    sk = getattr(model, f'skip_layer{j}')
+    return sk[0](fuse) if len(sk) else fuse
+
+
 R34_FLOP = [0, 3.27, 7.27, 13.15, 16.02]
 R34_DEPTH_ENC_FLOP = [0.2506752, 3.1113216, 6.9470208, 12.66432, 15.538944]
 R34_TOTAL_FLOP = [22.37101509, 25.23166149, 29.06736069, 34.78465989, 37.65928389]
@@ -103,10 +142,7 @@ class SkipGateESANet(nn.Module):
         if activation.lower() != 'relu':
             raise NotImplementedError('Only relu is implemented as activation on the HIP path. '
                                       'Got {}'.format(activation))
-        if upsampling != 'learned-3x3-zeropad':
-            raise NotImplementedError('Only learned-3x3-zeropad upsampling is implemented. Got {}'.format(upsampling))
-        if encoder_decoder_fusion != 'add':
-            raise NotImplementedError('Only encoder_decoder_fusion="add" is implemented')
+        check_decoder_options(upsampling, encoder_decoder_fusion)
         if fuse_depth_in_rgb_encoder not in ('add', 'SE-add'):
             raise NotImplementedError('fuse_depth_in_rgb_encoder must be "add" or "SE-add"')
         self.fuse_depth_in_rgb_encoder = fuse_depth_in_rgb_encoder
@@ -129,14 +165,8 @@ class SkipGateESANet(nn.Module):
                                     enc.down_16_channels_out, enc.down_32_channels_out)):
                 setattr(self, f'se_layer{j}', SqueezeAndExciteFusionAdd(ch))
 
-        for j, (cin, cout) in enumerate(((enc.down_4_channels_out, channels_decoder[2]),
-                                         (enc.down_8_channels_out, channels_decoder[1]),
-                                         (enc.down_16_channels_out, channels_decoder[0])), start=1):
-            setattr(self, f'skip_layer{j}', nn.Sequential(*([ConvBNAct(cin, cout, 1)] if cin != cout else [])))
-
-        self.context_module, ch_ctx = get_context_module(context_module, self.channels_decoder_in,
-                                                         channels_decoder[0])
-        self.decoder = Decoder(ch_ctx, channels_decoder, nr_decoder_blocks, num_classes)
+        build_decoder_side(self, channels_decoder, nr_decoder_blocks, num_classes, context_module, upsampling,
+                           encoder_decoder_fusion)
 
         self.temp = temp
         self.gate_layer = GlobalGate(branch_num=5)
@@ -346,8 +376,7 @@ class SkipGateESANet(nn.Module):
                     r = getattr(er, f'forward_layer{j}')(r_in)
                     fuse, d = r, None                # every sample skips depth from here on
                 if j < 4:
-                    sk = getattr(self, f'skip_layer{j}')
-                    skips.append(sk[0](fuse) if len(sk) else fuse)
+                    skips.append(decoder_skip(self, j, fuse))
         else:
             wcs = ops.fan_out(wcum, 4)               # one cumulative-weight column per stage
             for j in (1, 2, 3, 4):
@@ -361,10 +390,11 @@ class SkipGateESANet(nn.Module):
                     d_f, d = ops.fan_out(d, 2)       # stage-j depth features: fusion + next depth stage
                 # stage j<4: w*rgb + (1-w)*fused with w = sum_{k<j} weight[:,k];  stage 4: w = 1-weight[:,4]
                 fuse = ops.se_fuse_blend(r, d_f, self._se(j), wcs[j - 1], j - 1)
-                if j < 4:
+                if j < 4 and self.encoder_decoder_fusion == 'add':
                     fuse, f_skip = ops.fan_out(fuse, 2)   # fused map: next RGB stage + decoder skip connection
-                    sk = getattr(self, f'skip_layer{j}')
-                    skips.append(sk[0](f_skip) if len(sk) else f_skip)
+                    skips.append(decoder_skip(self, j, f_skip))
+                elif j < 4:
+                    skips.append(None)
         out = self.context_module(fuse)
         out = self.decoder([out, skips[2], skips[1], skips[0]], unpermute=unpermute)
 

@@ -18,11 +18,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .blocks import ConvBNAct, ResNetEncoder
-from .context import get_context_module
-from .decoder import Decoder
+from .blocks import ResNetEncoder
 from .fusion import SqueezeAndExciteFusionAdd, SqueezeAndExciteReweigh
-from .net import encoder_stage_pair
+from .net import build_decoder_side, check_decoder_options, decoder_skip, encoder_stage_pair
 
 
 class SkipESANet(nn.Module):
@@ -38,10 +36,7 @@ class SkipESANet(nn.Module):
         if activation.lower() != 'relu':
             raise NotImplementedError('Only relu is implemented as activation on the HIP path. '
                                       'Got {}'.format(activation))
-        if upsampling != 'learned-3x3-zeropad':
-            raise NotImplementedError('Only learned-3x3-zeropad upsampling is implemented. Got {}'.format(upsampling))
-        if encoder_decoder_fusion != 'add':
-            raise NotImplementedError('Only encoder_decoder_fusion="add" is implemented')
+        check_decoder_options(upsampling, encoder_decoder_fusion)
         self.fuse_depth_in_rgb_encoder = fuse_depth_in_rgb_encoder
         self.block_rule = block_rule if block_rule else [1, 1, 1, 1]
         self.height, self.width = height, width
@@ -67,14 +62,8 @@ class SkipESANet(nn.Module):
         for j in range(4):
             setattr(self, f'gate_layer{j}', SqueezeAndExciteReweigh(self.temp, stage_ch[j]))
 
-        for j, (cin, cout) in enumerate(((enc.down_4_channels_out, channels_decoder[2]),
-                                         (enc.down_8_channels_out, channels_decoder[1]),
-                                         (enc.down_16_channels_out, channels_decoder[0])), start=1):
-            setattr(self, f'skip_layer{j}', nn.Sequential(*([ConvBNAct(cin, cout, 1)] if cin != cout else [])))
-
-        self.context_module, ch_ctx = get_context_module(context_module, self.channels_decoder_in,
-                                                         channels_decoder[0])
-        self.decoder = Decoder(ch_ctx, channels_decoder, nr_decoder_blocks, num_classes)
+        build_decoder_side(self, channels_decoder, nr_decoder_blocks, num_classes, context_module, upsampling,
+                           encoder_decoder_fusion)
 
         self.hard_gate = False
         self.ini_stage = False
@@ -189,8 +178,7 @@ class SkipESANet(nn.Module):
                     fuse = ops.batch_merge(r, fused, mapping.to(dev))
             if j < 4:
                 weights.append(wj)
-                sk = getattr(self, f'skip_layer{j}')
-                skips.append(sk[0](fuse) if len(sk) else fuse)
+                skips.append(decoder_skip(self, j, fuse))
         if self.save_weight_info:
             for j in range(4):
                 self.weight_list[j] = torch.cat((self.weight_list[j], weights[j].detach().cpu()))
@@ -229,7 +217,6 @@ class SkipESANet(nn.Module):
                 prev = w[:, 1]
             fuse, w = self._fuse(j, r, d, wb, mode, prev, test)
             if j < 4:
-                sk = getattr(self, f'skip_layer{j}')
-                skips.append(sk[0](fuse) if len(sk) else fuse)
+                skips.append(decoder_skip(self, j, fuse))
         out = self.context_module(fuse)
         return self.decoder([out, skips[2], skips[1], skips[0]])

@@ -1382,17 +1382,16 @@ def nearest_concat(x, *ys):
 
 class _Upsample2xDw(Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, skip):
+    def forward(ctx, x, weight, bias, skip, replicate):
         lib = _lib()
         x, weight, bias, skip = _chk(x, 'x'), _chk(weight, 'weight'), _chk(bias, 'bias'), _chk(skip, 'skip')
         N, Cc, H, W = x.shape
-        if skip is not None and tuple(skip.shape) != (N, Cc, 2 * H, 2 * W):
-            raise L.DynmmHipError(f'upsample skip connection {tuple(skip.shape)} does not match the upsampled '
-                                  f'feature map {(N, Cc, 2 * H, 2 * W)} (input H, W must be multiples of 32)')
+        _check_up_skip(skip, N, Cc, H, W)
         y = torch.empty((N, Cc, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
-        L.check(lib.dynmm_upsample2x_dw3x3_fwd(_p(x), _p(weight), _p(bias), _p(skip), _p(y), N, Cc, H, W,
-                                               _stream()), 'upsample_fwd')
+        fwd = lib.dynmm_upsample2x_dw3x3_rep_fwd if replicate else lib.dynmm_upsample2x_dw3x3_fwd
+        L.check(fwd(_p(x), _p(weight), _p(bias), _p(skip), _p(y), N, Cc, H, W, _stream()), 'upsample_fwd')
         ctx.save_for_backward(x, weight)
+        ctx.replicate = replicate
         ctx.has_bias = bias is not None
         ctx.has_skip = skip is not None
         ctx.w_param, ctx.b_param = weight, bias
@@ -1414,15 +1413,129 @@ class _Upsample2xDw(Function):
         if dw is not None:
             nb = lib.dynmm_upsample2x_dw3x3_bwd_workspace_bytes(N, Cc)
             ws = torch.empty(max(nb // 4, 1), device=g.device, dtype=torch.float32)
+        if ctx.replicate:
+            g = _aligned16(g)
+            L.check(lib.dynmm_upsample2x_dw3x3_rep_bwd(_p(g), _p(x), _p(weight), _p(dx), _p(dw), _p(db), _p(ws), N, Cc,
+                                                       H, W, _stream()), 'upsample_rep_bwd')
+            _grads_enqueued()
+            return dx, dw_ret, db_ret, (g if ctx.has_skip else None), None
         L.check(lib.dynmm_upsample2x_dw3x3_bwd(_p(g), _p(x), _p(weight), _p(dx), _p(dw), _p(db), _p(ws), N, Cc, H, W,
                                                _stream()), 'upsample_bwd')
         _grads_enqueued()
-        return dx, dw_ret, db_ret, (g if ctx.has_skip else None)
+        return dx, dw_ret, db_ret, (g if ctx.has_skip else None), None
 
 
-def upsample2x_dw3x3(x, weight, bias, skip=None):
-    """Learned 2x upsample (nearest + depthwise 3x3 + bias) fused with the decoder's skip add."""
-    return _Upsample2xDw.apply(x, weight, bias, skip)
+_BORDERS = ('zero', 'replicate')
+
+
+def upsample2x_dw3x3(x, weight, bias, skip=None, border='zero'):
+    """Learned 2x upsample (nearest + depthwise 3x3 + bias) fused with the decoder's skip add.  border='zero' is
+    'learned-3x3-zeropad' (conv padding 1), border='replicate' is 'learned-3x3' (ReplicationPad2d(1) + conv padding 0,
+    model.py:380-384)."""
+    if border not in _BORDERS:
+        raise NotImplementedError(f'upsample2x_dw3x3: border must be one of {_BORDERS}, got {border!r}')
+    return _Upsample2xDw.apply(x, weight, bias, skip, border == 'replicate')
+
+
+def _check_up_skip(skip, N, Cc, H, W):
+    if skip is not None and tuple(skip.shape) != (N, Cc, 2 * H, 2 * W):
+        raise L.DynmmHipError(f'upsample skip connection {tuple(skip.shape)} does not match the upsampled '
+                              f'feature map {(N, Cc, 2 * H, 2 * W)} (input H, W must be multiples of 32)')
+
+
+def _aligned16(t):
+    """t itself when its data is 16-byte aligned (the kernels' vector loads), else an aligned copy."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
+
+_UP_MODES = {'nearest': 0, 'bilinear': 1}     # DYNMM_UP_NEAREST / DYNMM_UP_BILINEAR
+
+
+class _Upsample2x(Function):
+    @staticmethod
+    def forward(ctx, x, skip, mode):
+        lib = _lib()
+        x, skip = _chk(x, 'x'), _aligned16(_chk(skip, 'skip'))
+        N, Cc, H, W = x.shape
+        _check_up_skip(skip, N, Cc, H, W)
+        y = torch.empty((N, Cc, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
+        L.check(lib.dynmm_upsample2x_fwd(_p(x), _p(skip), _p(y), N, Cc, H, W, _UP_MODES[mode], _stream()),
+                'upsample2x_fwd')
+        ctx.dims, ctx.mode, ctx.has_skip = (N, Cc, H, W), mode, skip is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib()
+        g = _aligned16(_chk(g, 'grad'))
+        N, Cc, H, W = ctx.dims
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((N, Cc, H, W), device=g.device, dtype=torch.float32)
+            L.check(lib.dynmm_upsample2x_bwd(_p(g), _p(dx), N, Cc, H, W, _UP_MODES[ctx.mode], _stream()),
+                    'upsample2x_bwd')
+        return dx, (g if ctx.has_skip else None), None
+
+
+def upsample2x(x, mode, skip=None):
+    """F.interpolate(x, (2H, 2W), mode) for mode 'nearest' / 'bilinear' (align_corners=False) (model.py:404-410), fused
+    with the decoder's skip add `out += encoder_features` (model.py:354-355) when skip is given."""
+    if mode not in _UP_MODES:
+        raise NotImplementedError(f'upsample2x: mode must be one of {tuple(_UP_MODES)}, got {mode!r}')
+    return _Upsample2x.apply(x, skip, mode)
+
+
+class _BilinearConcat(Function):
+    """cat([x, bilinear(y_1, size(x)), bilinear(y_2, size(x)), ...], dim=1), align_corners=False."""
+
+    @staticmethod
+    def forward(ctx, x, *ys):
+        lib = _lib()
+        st = _stream()
+        x = _chk(x, 'x')
+        ys = [_chk(y, 'y') for y in ys]
+        N, C0, H, W = x.shape
+        Ctot = C0 + sum(y.shape[1] for y in ys)
+        out = torch.empty((N, Ctot, H, W), device=x.device, dtype=torch.float32)
+        # x itself: the identity copy of dynmm_nearest_into_fwd
+        L.check(lib.dynmm_nearest_into_fwd(_p(x), _p(out), N, C0, H, W, Ctot, 0, H, W, st), 'nearest_into_fwd')
+        ctx.parts = [(C0, H, W, 0)]
+        off = C0
+        for t in ys:
+            _, Cc, h, w = t.shape
+            L.check(lib.dynmm_bilinear_into_fwd(_p(t), _p(out), N, Cc, h, w, Ctot, off, H, W, st), 'bilinear_into_fwd')
+            ctx.parts.append((Cc, h, w, off))
+            off += Cc
+        ctx.dims = (N, Ctot, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib()
+        st = _stream()
+        g = _chk(g, 'grad')
+        N, Ctot, H, W = ctx.dims
+        outs = []
+        for i, (Cc, h, w, off) in enumerate(ctx.parts):
+            if not ctx.needs_input_grad[i]:
+                outs.append(None)
+                continue
+            d = torch.empty((N, Cc, h, w), device=g.device, dtype=torch.float32)
+            fn, name = (lib.dynmm_nearest_into_bwd, 'nearest_into_bwd') if i == 0 else \
+                (lib.dynmm_bilinear_into_bwd, 'bilinear_into_bwd')
+            L.check(fn(_p(g), _p(d), N, Cc, h, w, Ctot, off, H, W, st), name)
+            outs.append(d)
+        return tuple(outs)
+
+
+def resize_concat(x, *ys, mode):
+    """cat([x, interpolate(y_1, size(x), mode), ...], dim=1): the pyramid pooling concat (context_modules.py:70-87,
+    :117-131) for mode 'nearest' (nearest_concat) or 'bilinear' (align_corners=False)."""
+    if mode == 'nearest':
+        return nearest_concat(x, *ys)
+    if mode != 'bilinear':
+        raise NotImplementedError(f'resize_concat: mode must be "nearest" or "bilinear", got {mode!r}')
+    return _BilinearConcat.apply(x, *ys)
 
 
 # ------------------------------------------------------------------------------------------------

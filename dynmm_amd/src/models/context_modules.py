@@ -1,2 +1,2 @@
 """Counterpart of FusionDynMM/src/models/context_modules.py."""
-from ...nn.context import PyramidPoolingModule, get_context_module  # noqa: F401
+from ...nn.context import AdaptivePyramidPoolingModule, PyramidPoolingModule, get_context_module  # noqa: F401

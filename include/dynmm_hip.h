@@ -313,6 +313,26 @@ size_t dynmm_upsample2x_dw3x3_bwd_workspace_bytes(int N, int C);
 int dynmm_upsample2x_dw3x3_bwd(const float* g, const float* x, const float* w,
                                float* dx, float* dw, float* db, float* workspace,
                                int N, int C, int H, int W, void* stream);
+/* The decoder's other resampling modes (model.py:360-410, context_modules.py:70-131; csrc/resample.hip).
+ * x2 'nearest' / 'bilinear' (align_corners=False) up-sampling, + skip when skip != NULL; the input gradient (the skip's
+ * gradient is g itself). */
+#define DYNMM_UP_NEAREST 0
+#define DYNMM_UP_BILINEAR 1
+int dynmm_upsample2x_fwd(const float* x, const float* skip, float* y, int N, int C, int H, int W, int mode, void* stream);
+int dynmm_upsample2x_bwd(const float* g, float* dx, int N, int C, int H, int W, int mode, void* stream);
+/* 'learned-3x3': nearest x2 + ReplicationPad2d(1) + depthwise 3x3 (padding 0) + bias [+ skip]; same arguments and
+ * workspace (dynmm_upsample2x_dw3x3_bwd_workspace_bytes) as the zero-pad entry points above. */
+int dynmm_upsample2x_dw3x3_rep_fwd(const float* x, const float* w, const float* b, const float* skip,
+                                   float* y, int N, int C, int H, int W, void* stream);
+int dynmm_upsample2x_dw3x3_rep_bwd(const float* g, const float* x, const float* w,
+                                   float* dx, float* dw, float* db, float* workspace,
+                                   int N, int C, int H, int W, void* stream);
+/* out[:, c_off:c_off+C] = bilinear_resize(y, (H,W), align_corners=False) — the bilinear counterpart of
+ * dynmm_nearest_into_fwd/bwd (pyramid pooling branches); the backward is a gather (deterministic). */
+int dynmm_bilinear_into_fwd(const float* y, float* out, int N, int C, int h, int w,
+                            int Ctot, int c_off, int H, int W, void* stream);
+int dynmm_bilinear_into_bwd(const float* g_out, float* dy, int N, int C, int h, int w,
+                            int Ctot, int c_off, int H, int W, void* stream);
 
 /* ---- SE fusion + gated blend (rgb_depth_fusion.py:22-26, model_utils.py:47-51, …globalgate.py:282-310) ---- */
 /* s[n,c] = mean_hw x[n,c,:]  for two tensors at once. */
