@@ -207,8 +207,11 @@ def test_learned_zeropad_is_unchanged_by_the_border_argument(shape):
 @pytest.mark.parametrize('grid,hw', [((b, b), (15, 20)) for b in (1, 2, 4, 5, 8)] +
                          [((2 * b, 2 * b), (30, 40)) for b in (1, 2, 4, 5, 8)] + [((1, 3), (5, 1)), ((3, 2), (3, 5))])
 def test_bilinear_resize_concat(grid, hw):
+    check_bilinear_resize_concat(grid, hw)
+
+
+def check_bilinear_resize_concat(grid, hw, N=2, C0=16, C1=8):
     from dynmm_amd import ops
-    N, C0, C1 = 2, 16, 8
     (hb, wb), (H, W) = grid, hw
     x, y1, y2 = rnd(N, C0, H, W, seed=1), rnd(N, C1, hb, wb, seed=2), rnd(N, C1, 1, 1, seed=3)
     refs = [t.double().requires_grad_(True) for t in (x, y1, y2)]

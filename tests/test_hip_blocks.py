@@ -1,6 +1,8 @@
 """GPU: block-level parity (forward, input gradient and every parameter gradient) of the HIP
-modules against the oracle's functional restatement, at the shapes where the blocks run in the
-96x128 / 480x640 models."""
+modules against the oracle's functional restatement: at the shapes where the blocks run in the
+96x128 model (batch 2-3), and — the cases named `..._at_benchmark_shapes` — at the stage shapes of the
+480x640 model at batch 4 (64 @ 120x160, 128 @ 60x80, 256 @ 30x40, 512 @ 15x20).  Larger batches of the
+convolutions themselves: tests/test_benchmark_geometry.py."""
 import contextlib
 
 import pytest
@@ -50,7 +52,8 @@ def hip_relu_decisions(trace, tau=1e-5):
     queues = {}
     for y in trace:
         queues.setdefault(tuple(y.shape), []).append((y > 0).cpu())
-    census = {'sites': 0, 'imposed': 0, 'outside_band': 0, 'queues': queues}
+    census = {'sites': 0, 'imposed': 0, 'outside_band': 0, 'queues': queues, 'first_outside': None}
+    ordinal = {}
     orig = O.F.relu
 
     def relu(v, inplace=False):
@@ -65,6 +68,9 @@ def hip_relu_decisions(trace, tau=1e-5):
         census['sites'] += 1
         census['imposed'] += int((dis & band).sum())
         census['outside_band'] += int((dis & ~band).sum())
+        ordinal[tuple(v.shape)] = ordinal.get(tuple(v.shape), -1) + 1
+        if census['first_outside'] is None and bool((dis & ~band).any()):       # where a wrong mask / tap / residual starts
+            census['first_outside'] = (tuple(v.shape), ordinal[tuple(v.shape)], int((dis & ~band).sum()))
         return v * torch.where(band, hip, own).to(v.dtype)
     O.F.relu = relu
     try:
@@ -95,7 +101,8 @@ def run_pair(module, ref_fn, inputs, training=True, prefix='m'):
     with hip_relu_decisions(trace) as census:
         out_ref = ref_fn(sd, *xs_ref, training)
     outs_ref = [o for o in (out_ref if isinstance(out_ref, tuple) else (out_ref,)) if o is not None]
-    assert census['outside_band'] == 0, f'{census["outside_band"]} ReLU decisions differ from the fp64 oracle away from zero'
+    assert census['outside_band'] == 0, (f'{census["outside_band"]} ReLU decisions differ from the fp64 oracle away from zero; '
+                                         f'first at (activation shape, ordinal among that shape, count): {census["first_outside"]}')
     assert not any(census['queues'].values()), 'traced HIP ReLU outputs the oracle never matched'
     gs = [rnd(*o.shape, seed=11 + i) for i, o in enumerate(outs_ref)]
     torch.autograd.backward(outs_ref, [g.double() for g in gs])
@@ -140,6 +147,39 @@ def run_pair(module, ref_fn, inputs, training=True, prefix='m'):
 def test_non_bottleneck_1d(c, h, w, n, training):
     from dynmm_amd.nn.blocks import NonBottleneck1D
     run_pair(NonBottleneck1D(c, c), lambda sd, x, tr: O.non_bottleneck_1d(sd, 'm', x, tr), [rnd(n, c, h, w)], training)
+
+
+@pytest.mark.parametrize('c,h,w', [(64, 120, 160), (128, 60, 80), (256, 30, 40), (512, 15, 20)])
+@pytest.mark.parametrize('training', [True, False])
+def test_non_bottleneck_1d_at_benchmark_shapes(c, h, w, training):
+    """The fused chain as the optimisation step runs it at 480x640, batch 4: statistics out of the producing convolution, bn1's
+    reductions out of conv3x1_2's input gradient, ReLU decisions as bits, F(4,3) with mask and accumulate."""
+    from dynmm_amd.nn.blocks import NonBottleneck1D
+    run_pair(NonBottleneck1D(c, c), lambda sd, x, tr: O.non_bottleneck_1d(sd, 'm', x, tr), [rnd(4, c, h, w)], training)
+
+
+def test_basic_block_at_benchmark_shape():
+    from dynmm_amd.nn.blocks import BasicBlock
+    run_pair(BasicBlock(64, 64), lambda sd, x, tr: O.basic_block(sd, 'm', x, tr), [rnd(4, 64, 120, 160)])
+
+
+@pytest.mark.parametrize('blk', ['NonBottleneck1D', 'BasicBlock'])
+def test_strided_block_with_downsample_at_benchmark_shape(blk):
+    """64 @ 120x160 -> 128 @ 60x80, the first block of stage 2 with its down-sampling 1x1."""
+    import torch.nn as nn
+    from dynmm_amd.nn import blocks
+    down = nn.Sequential(nn.Conv2d(64, 128, 1, stride=2, bias=False), nn.BatchNorm2d(128))
+    m = blocks.BLOCKS[blk](64, 128, 2, down)
+    fn = O.non_bottleneck_1d if blk == 'NonBottleneck1D' else O.basic_block
+    run_pair(m, lambda sd, x, tr: fn(sd, 'm', x, tr, 2), [rnd(4, 64, 120, 160)])
+
+
+@pytest.mark.parametrize('h,w', [(30, 40), (60, 80)])
+def test_decoder_module_at_benchmark_shapes(h, w):
+    """DecoderModule(128, 128, 3, 40) with input 128 @ 30x40 / skip 128 @ 60x80 (decoder module 2) and 60x80 / 120x160 (module 3)."""
+    from dynmm_amd.nn.decoder import DecoderModule
+    run_pair(DecoderModule(128, 128, 3, 40), lambda sd, x, skip, tr: O.decoder_module(sd, 'm', x, skip, tr, 3),
+             [rnd(4, 128, h, w), rnd(4, 128, 2 * h, 2 * w, seed=5)])
 
 
 @pytest.mark.parametrize('blk', ['NonBottleneck1D', 'BasicBlock'])
