@@ -103,12 +103,11 @@ class GradBucketReducer:
         self.pending_scale = 1.0                             # 1/world still owed to the flat buffer after finish(average=False)
         if self.overlap:
             # (a) plain autograd accumulation (torch modules): post-accumulate hooks;
-            # (b) the HIP kernels' in-place gradient protocol (ops.DIRECT_GRAD: autograd never sees these
-            #     gradients, so hooks never fire): ops reports every parameter whose gradient kernels are enqueued.
+            # (b) the HIP kernels' in-place gradient protocol (ops.step_scope: autograd never sees these gradients, so
+            #     hooks never fire): ops reports every parameter whose gradient kernels are enqueued to the step's
+            #     `on_grad_written` — the owner of this reducer passes _on_grad_written there.
             for p in self.params:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad_ready))
-            from . import ops
-            ops.GRAD_READY_HOOK = self._on_grad_written
 
     # -- step protocol --------------------------------------------------------------------------
     def zero(self):
@@ -168,7 +167,7 @@ class GradBucketReducer:
         # it, i.e. also under the in-place gradient protocol; there the kernels report completion themselves (with
         # the streams they were launched on), so the hook must stay out of the way
         from . import ops
-        if ops.DIRECT_GRAD:
+        if ops.in_step():
             return
         self._arrived(p)
 
@@ -215,9 +214,6 @@ class GradBucketReducer:
         for h in self._hooks:
             h.remove()
         self._hooks = []
-        from . import ops
-        if ops.GRAD_READY_HOOK == self._on_grad_written:
-            ops.GRAD_READY_HOOK = None
 
 
 def broadcast_parameters(module, src=0, process_group=None):

@@ -9,12 +9,12 @@
   evaluate   = FusionDynMM/eval.py:104-146 — forward(test=True), bilinear resize to the label size,
                arg-max, void mask, confusion matrix, mIoU*100.
 """
-import contextlib
 import ctypes as C
 
 import torch
 
 from . import dp, ops
+from . import ops_seq as S
 from . import lib as L
 
 
@@ -24,7 +24,7 @@ class FlatParameters:
     element for element the layout of dp.GradBucketReducer's flat gradient buffer.  align > 1 (elements): every parameter
     starts on a multiple of `align` (zero padding between them; kernels that stage weights with 16-byte loads —
     csrc/seq_ffn.hip — need align = 4): such a buffer does NOT match the reducer's packed layout and needs a gradient buffer
-    laid out with the same spans (AffectTrainStep allocates its own; _FlatOptimizer asserts equal sizes)."""
+    laid out with the same spans (FlatAdamWStep allocates its own; _FlatOptimizer asserts equal sizes)."""
 
     def __init__(self, params, align=1):
         self.params = list(params)
@@ -70,7 +70,7 @@ class _FlatOptimizer:
 
     * torch.optim semantics for parameters that took no part in a step (`.grad is None` there): they are
       skipped — no weight decay, no momentum update.  The kernels that write gradients report the
-      parameters they touched (ops.touched()); `step(touched)` updates only those element ranges.
+      parameters they touched (the `touched` set of ops.step_scope's Step); `step(touched)` updates only those element ranges.
     * `groups`: {name: [params]} partitions the parameters into sets that may start receiving gradients
       at different times (the gate vs everything else: ini_stage / baseline epochs, --freeze); Adam keeps
       one device step counter per group so its bias correction matches torch's per-parameter counters.
@@ -257,20 +257,76 @@ class Adam(_FlatOptimizer):
         return [self.m, self.v, self.steps]
 
 
-@contextlib.contextmanager
-def direct_gradients(async_wgrad):
-    """Scope of the in-place gradient protocol (ops.DIRECT_GRAD / ops.ASYNC_WGRAD): inside, backward kernels
-    OVERWRITE the `.grad` views (one backward per zero()) and return None to autograd; outside, every other
-    backward in the process keeps torch's accumulate semantics."""
-    saved = (ops.DIRECT_GRAD, ops.ASYNC_WGRAD)
-    ops.DIRECT_GRAD, ops.ASYNC_WGRAD = True, bool(async_wgrad)
-    try:
-        yield
-    finally:
-        try:
-            ops.flush_wgrad_groups()         # nothing queued may outlive the protocol's scope
-        finally:
-            ops.DIRECT_GRAD, ops.ASYNC_WGRAD = saved
+class FlatAdamWStep:
+    """One iteration of Supervised_Learning.train's loop for a modality-level model: zero, new dropout masks, forward + objective
+    + backward (the subclass's `_backward`), clip_grad_norm_(clip_val), AdamW — flat parameter / gradient / moment buffers, the
+    kernels write parameter gradients straight into `flat_g`, the clip coefficient and the non-finite-loss guard stay on the
+    device.  use_graph: the step is replayed as ONE hipGraph (lr / step counter are device scalars; whatever else a capture
+    freezes belongs in the subclass's `_graph_key`, and the capture is re-made when it changes).
+
+    A subclass supplies `_backward(inputs, target) -> (loss the optimizer's guard inspects, dict for self.last)` and, when it
+    captures, `_graph_key`, `_clone_inputs`, `_input_tensors` and optionally `_extra_state`."""
+
+    def __init__(self, model, lr, weight_decay, clip_val=8.0, use_graph=False, prepack=None, wgrad_group=None):
+        self.model = model
+        params = [p for p in model.parameters() if p.requires_grad]
+        if not params:
+            raise ValueError(f'{type(self).__name__}: the model has no trainable parameter')
+        self.flatp = FlatParameters(params, align=4)      # 16-byte aligned weights for the fused feed-forward kernel
+        self.flat_g = torch.zeros_like(self.flatp.flat)
+        for p in params:
+            lo, hi = self.flatp.span[id(p)]
+            p.grad = self.flat_g[lo:hi].view_as(p)
+        self.opt = Adam(self.flatp, self.flat_g, lr, weight_decay=weight_decay, decoupled=True)   # AdamW
+        self.clip_val = float(clip_val)
+        self.last = None
+        self.use_graph = bool(use_graph)
+        self._graphs = {}
+        # every Linear / Conv1d weight of the step re-laid for the MFMA kernels by ONE launch (ops.PackedWeights) instead of
+        # one pack launch per layer call (r2 profile: 2 310 of 14 525 dispatches were pack_weight_kernel)
+        self.prepack = prepack
+        self.wgrad_group = wgrad_group       # (attribute: A/B against the library's default; 8 = its group limit)
+
+    def _extra_state(self):
+        """tensors besides the parameters and the optimizer state that a capture's warm-up step must not change"""
+        return []
+
+    def _body(self, inputs, target):
+        self.flat_g.zero_()
+        S.advance_dropout_step(self.flat_g.device)   # new dropout masks every step (also under hipGraph replay)
+        with ops.step_scope(prepack=self.prepack, wgrad_group=self.wgrad_group):
+            loss, self.last = self._backward(inputs, target)
+        nc = S.clip_grad_norm(self.flat_g, self.clip_val)
+        self.opt.grad_scale_dev = nc[1:2]
+        self.opt.step(None, loss)
+        self.last['grad_norm'] = nc[0:1]
+
+    def __call__(self, inputs, target):
+        if not self.use_graph:
+            self._body(inputs, target)
+            return self.last
+        key = self._graph_key(inputs, target)
+        entry = self._graphs.get(key)
+        if entry is None:
+            static_in, static_y = self._clone_inputs(inputs), target.clone()
+            state = [self.flatp.flat] + self._extra_state() + self.opt.state_tensors()
+            snap = [t.clone() for t in state]
+            self._body(static_in, static_y)                  # warm-up outside capture (allocator, lazy init)
+            for t, c in zip(state, snap):
+                t.copy_(c)                                   # undo the warm-up's update
+            if self.prepack is not None and self.prepack.reg and self.prepack.dirty:
+                self.prepack._layout()                       # the warm-up registered the weights: lay the arena out before capturing
+            graph = torch.cuda.CUDAGraph()
+            with ops.capture_scope(), torch.cuda.graph(graph):
+                self._body(static_in, static_y)
+            entry = self._graphs[key] = (graph, static_in, static_y, self.last)
+        graph, static_in, static_y, static_last = entry
+        for a, b in zip(self._input_tensors(static_in), self._input_tensors(inputs)):
+            a.copy_(b)
+        static_y.copy_(target)
+        graph.replay()
+        self.last = {k: v.clone() for k, v in static_last.items()}
+        return self.last
 
 
 class TrainStep:
@@ -304,7 +360,7 @@ class TrainStep:
         self.opt.param_index, self.opt.n_params = {id(q): i for i, q in enumerate(allp)}, len(allp)
         # 3-stream schedule: RGB encoder | depth encoder | conv weight gradients (see nn/net.py, ops.py)
         self.multi_stream = bool(multi_stream)
-        # None: on unless DYNMM_NO_FUSED_TAIL is set (A/B switch for bench.py / tests)
+        # the decoder's last up-sampling + full-resolution CE as one kernel pair; None = on (False: A/B switch for bench.py / tests)
         self.fuse_tail = True if fuse_tail is None else bool(fuse_tail)
         self.prepack = ops.PackedWeights() if prepack else None
         if hasattr(model, 'dual_stream'):
@@ -319,8 +375,11 @@ class TrainStep:
     # ------------------------------------------------------------------------------------------------
     def _body(self, rgb, depth, targets):
         dec = getattr(self.model, 'decoder', None) if self.fuse_tail else None
-        with direct_gradients(self.multi_stream), self._prepacked():
-            ops.touched_reset()
+        red = self.reducer
+        # all conv weights of the step packed by one launch (ops.PackedWeights; per-conv packs on the first step); gradients
+        # written in place, and reported to the reducer as their kernels are enqueued
+        with ops.step_scope(prepack=self.prepack, async_wgrad=self.multi_stream,
+                            on_grad_written=red._on_grad_written if red.overlap else None) as step:
             ops.stream_census_reset()
             self.reducer.zero()
             if dec is not None:
@@ -336,7 +395,6 @@ class TrainStep:
                 outs, lf = res, torch.zeros((), device=rgb.device)   # SkipESANet: the four outputs only
             # weighted 4-scale CE, total-loss rule and the seeds of the backward pass on the device (no PyTorch
             # arithmetic kernels between the forward and the backward of the model)
-            red = self.reducer
             shared = (red.world > 1 or red.force) and red.enabled
             # data parallel: the total is written into the slot that rides in the last gradient bucket, so after
             # finish() it holds the mean over ranks and every rank takes the same non-finite-loss decision
@@ -344,23 +402,8 @@ class TrainStep:
                                                       self.loss_ratio, self.flop_budget,
                                                       total_out=red.loss_slot if shared else None)
             self.last['loss_flop'] = lf.detach()
-            ops.join_async()
-            self._touched = ops.touched_ids()
-            self.census = ops.stream_census(check=True)     # raises on a fifth busy stream (ops.MAX_BUSY_STREAMS)
-
-    @contextlib.contextmanager
-    def _prepacked(self):
-        """all conv weights of the step packed by one launch (ops.PackedWeights); per-conv packs on the first step"""
-        prev = ops.PREPACK
-        ops.PREPACK = self.prepack
-        if self.prepack is not None:
-            self.prepack.pack()
-        try:
-            yield
-        finally:
-            if self.prepack is not None:
-                self.prepack.invalidate()
-            ops.PREPACK = prev
+        self._touched = frozenset(step.touched)
+        self.census = ops.stream_census(check=True)     # raises on a fifth busy stream (ops.MAX_BUSY_STREAMS)
 
     def _rank_dependent_touch(self):
         """Can the set of parameters that received a gradient differ between ranks?  Dense execution launches the

@@ -126,94 +126,43 @@ def _leaves(x):
     return [x] if torch.is_tensor(x) and x.is_cuda else []
 
 
-class ExpertTrainStep:
-    """One iteration of Supervised_Learning.train's loop for ONE model (no moe_model, no additional loss): forward, the
-    objective ('bce': BCEWithLogitsLoss, 'l1': L1Loss) and its backward seed in one kernel (ops_mlp.head_loss), backward,
-    clip_grad_norm_(clip_val), AdamW.  Flat parameter / gradient / moment buffers; the kernels write parameter gradients
-    straight into the flat gradient buffer; the clip coefficient and the non-finite-loss guard stay on the device; new
-    dropout masks every step.  `loss_acc` (fp64 device [1]) collects loss * B of every step, so an epoch's training loss
-    costs one host read.  use_graph: replay the step as one hipGraph (models without BatchNorm: a capture's warm-up step
-    would update running statistics)."""
+class ExpertTrainStep(engine.FlatAdamWStep):
+    """engine.FlatAdamWStep for ONE model (no moe_model, no additional loss): the objective ('bce': BCEWithLogitsLoss, 'l1':
+    L1Loss) and its backward seed come out of one kernel (ops_mlp.head_loss).  `loss_acc` (fp64 device [1]) collects loss * B
+    of every step, so an epoch's training loss costs one host read.  use_graph: only for models without BatchNorm (a capture's
+    warm-up step would update running statistics)."""
 
     def __init__(self, model, objective, lr, weight_decay, clip_val=8.0, use_graph=False):
         if objective not in M.HEAD_LOSSES:
             raise ValueError(f'objective must be one of {sorted(M.HEAD_LOSSES)}, got {objective!r}')
-        self.model, self.objective = model, objective
-        params = [p for p in model.parameters() if p.requires_grad]
-        if not params:
-            raise ValueError('ExpertTrainStep: the model has no trainable parameter')
-        self.flatp = engine.FlatParameters(params, align=4)     # 16-byte aligned weights for the fused feed-forward kernel
-        self.flat_g = torch.zeros_like(self.flatp.flat)
-        for p in params:
-            lo, hi = self.flatp.span[id(p)]
-            p.grad = self.flat_g[lo:hi].view_as(p)
-        self.opt = engine.Adam(self.flatp, self.flat_g, lr, weight_decay=weight_decay, decoupled=True)   # AdamW
-        self.clip_val = float(clip_val)
-        self.loss_acc = torch.zeros(1, device=self.flat_g.device, dtype=torch.float64)
-        self.last = None
         depth = [len(m.layers) for m in model.modules() if isinstance(m, nn.TransformerEncoder)]
         self.has_bn = any(isinstance(m, nn.BatchNorm1d) for m in model.modules())
         if use_graph and self.has_bn:
             raise ValueError('ExpertTrainStep(use_graph=True): only for models without BatchNorm (the transformer experts)')
-        self.use_graph = bool(use_graph)
-        self._graphs = {}
         # the transformer experts take AffectTrainStep's launch savings: one weight re-layout launch per step and grouped
         # weight-gradient launches per same-shape layer stack
-        self.prepack = ops.PackedWeights() if depth else None
-        self.wgrad_group = min(8, max(depth)) if depth else None
+        super().__init__(model, lr, weight_decay, clip_val, use_graph, prepack=ops.PackedWeights() if depth else None,
+                         wgrad_group=min(8, max(depth)) if depth else None)
+        self.objective = objective
+        self.loss_acc = torch.zeros(1, device=self.flat_g.device, dtype=torch.float64)
 
-    def _body(self, inputs, target):
-        m = self.model
-        self.flat_g.zero_()
-        S.advance_dropout_step(self.flat_g.device)      # new dropout masks every step (also under hipGraph replay)
-        prev, prev_group = ops.PREPACK, ops.WGRAD_GROUP
-        if self.prepack is not None:
-            ops.PREPACK = self.prepack
-            ops.WGRAD_GROUP = max(ops.WGRAD_GROUP, self.wgrad_group)
-            self.prepack.pack()
-        try:
-            with engine.direct_gradients(False):        # kernels write parameter gradients straight into flat_g
-                ops.touched_reset()
-                out = m(inputs)
-                loss, seed = M.head_loss(out, target, self.objective, seed=True, loss_acc=self.loss_acc)
-                torch.autograd.backward([out], [seed])
-                A.join_branches()
-        finally:
-            if self.prepack is not None:
-                self.prepack.invalidate()               # the optimizer below rewrites the weights
-            ops.PREPACK, ops.WGRAD_GROUP = prev, prev_group
-        nc = S.clip_grad_norm(self.flat_g, self.clip_val)
-        self.opt.grad_scale_dev = nc[1:2]
-        self.opt.step(None, loss)
-        self.last = {'out': out.detach(), 'loss': loss, 'grad_norm': nc[0:1]}
+    def _backward(self, inputs, target):
+        out = self.model(inputs)
+        loss, seed = M.head_loss(out, target, self.objective, seed=True, loss_acc=self.loss_acc)
+        torch.autograd.backward([out], [seed])
+        A.join_branches()
+        return loss, {'out': out.detach(), 'loss': loss}
 
-    def __call__(self, inputs, target):
-        if not self.use_graph:
-            self._body(inputs, target)
-            return self.last
-        key = (tuple(tuple(t.shape) for t in _leaves(inputs)), tuple(target.shape), bool(self.model.training))
-        entry = self._graphs.get(key)
-        if entry is None:
-            static_in = _map(inputs, lambda t: t.clone())
-            static_y = target.clone()
-            snap = [t.clone() for t in [self.flatp.flat, self.loss_acc] + self.opt.state_tensors()]
-            self._body(static_in, static_y)                     # warm-up outside capture (allocator, lazy init)
-            for t, c in zip([self.flatp.flat, self.loss_acc] + self.opt.state_tensors(), snap):
-                t.copy_(c)                                      # undo the warm-up's update and loss
-            if self.prepack is not None and self.prepack.reg and self.prepack.dirty:
-                self.prepack._layout()                          # lay the weight arena out before capturing
-            graph = torch.cuda.CUDAGraph()
-            with ops.capture_scope(), torch.cuda.graph(graph):
-                self._body(static_in, static_y)
-            entry = (graph, static_in, static_y, self.last)
-            self._graphs[key] = entry
-        graph, static_in, static_y, static_last = entry
-        for a, b in zip(_leaves(static_in), _leaves(inputs)):
-            a.copy_(b)
-        static_y.copy_(target)
-        graph.replay()
-        self.last = {k: v.clone() for k, v in static_last.items()}
-        return self.last
+    def _extra_state(self):
+        return [self.loss_acc]
+
+    def _graph_key(self, inputs, target):
+        return (tuple(tuple(t.shape) for t in _leaves(inputs)), tuple(target.shape), bool(self.model.training))
+
+    def _clone_inputs(self, inputs):
+        return _map(inputs, lambda t: t.clone())
+
+    _input_tensors = staticmethod(_leaves)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

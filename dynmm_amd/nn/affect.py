@@ -32,7 +32,7 @@ row launches nothing).  Training, the soft gate, infer_mode != 0 and anything un
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import engine, ops
 from .. import ops_mlp as M
 from .. import ops_seq as S
 
@@ -64,7 +64,6 @@ def run_branches(fns):
     fork = torch.cuda.Event()
     fork.record(main)
     if torch.cuda.is_current_stream_capturing():
-        from .. import ops
         ops._CAPTURE_EVENTS.append(fork)           # an event recorded into a capture must outlive it (ops._queue_wgrad)
     first = fns[0]()                               # host order = list order (the injected-mask tests count calls)
     outs = []
@@ -85,7 +84,6 @@ def run_branches(fns):
 
 def join_branches():
     """After a backward pass: the calling stream waits for every branch stream (their nodes ran there)."""
-    from .. import ops
     ops.flush_wgrad_groups()                       # queued weight-gradient groups go out on their branch's stream
     if _ALL:
         main = torch.cuda.current_stream()
@@ -369,88 +367,33 @@ class DynMMNet(_GatedMixture):
         return tmp[2].item()
 
 
-class AffectTrainStep:
-    """One iteration of Supervised_Learning.train's loop (:104-144) for a DynMM mixture (`moe_model`,
-    additional_loss=True): forward, L1 objective + lossw * gate regulariser, backward, clip_grad_norm_(8), AdamW —
-    flat parameter / gradient / moment buffers, loss + backward seeds + clip coefficient computed on the device."""
+class AffectTrainStep(engine.FlatAdamWStep):
+    """engine.FlatAdamWStep for a DynMM mixture (`moe_model`, additional_loss=True; Supervised_Learning.train :104-144): L1
+    objective + lossw * gate regulariser, with the loss and the backward seeds computed on the device.  The step is ~700 small
+    launches (5-layer transformers on 50-token sequences), launch-bound when issued eagerly: hence use_graph (temp, hard_gate
+    and the batch shape are frozen into a capture)."""
 
     def __init__(self, model, lr=1e-6, weight_decay=1e-4, lossw=0.0, clip_val=8.0, use_graph=False):
-        from .. import engine
-        self.model = model
-        params = [p for p in model.parameters() if p.requires_grad]
-        self.flatp = engine.FlatParameters(params, align=4)      # 16-byte aligned weights for the fused feed-forward kernel
-        self.flat_g = torch.zeros_like(self.flatp.flat)
-        for p in params:
-            lo, hi = self.flatp.span[id(p)]
-            p.grad = self.flat_g[lo:hi].view_as(p)
-        self.opt = engine.Adam(self.flatp, self.flat_g, lr, weight_decay=weight_decay, decoupled=True)   # AdamW
-        self.lossw, self.clip_val = float(lossw), float(clip_val)
-        self.last = None
-        depth = max([len(m.layers) for m in model.modules() if isinstance(m, nn.TransformerEncoder)] or [1])
-        self.wgrad_group = min(8, depth)                       # (attribute: A/B against the library's default; 8 = its group limit)
-        # The step is ~700 small launches (5-layer transformers on 50-token sequences): launch-bound when issued
-        # eagerly, so it can be replayed as ONE hipGraph (lr / step counter are device scalars; temp, hard_gate and
-        # the batch shape are frozen into a capture, which is re-made when they change).
-        self.use_graph = bool(use_graph)
-        self._graphs = {}
-        # every Linear / Conv1d weight of the step re-laid for the MFMA kernels by ONE launch (ops.PackedWeights) instead of
-        # one pack launch per layer call (r2 profile: 2 310 of 14 525 dispatches were pack_weight_kernel)
-        from .. import ops
-        self.prepack = ops.PackedWeights()
-
-    def _body(self, inputs, target):
-        from .. import engine, ops
-        m = self.model
-        self.flat_g.zero_()
-        S.advance_dropout_step(self.flat_g.device)   # new dropout masks every step (also under hipGraph replay)
-        prev, ops.PREPACK = ops.PREPACK, self.prepack
         # a transformer is num_layers same-shape layers on one stream: its linear1 / linear2 / in_proj / out_proj weight gradients go
         # out as ONE grouped launch each (the library's default group of 4 left every fifth layer to a launch of its own, split
         # 16 ways over the pixel range to fill the chip)
-        prev_group, ops.WGRAD_GROUP = ops.WGRAD_GROUP, max(ops.WGRAD_GROUP, self.wgrad_group)
-        self.prepack.pack()
-        try:
-            with engine.direct_gradients(False):     # kernels write parameter gradients straight into flat_g
-                ops.touched_reset()
-                logits, preds = m.gate_and_experts(inputs)
-                self.last = S.moe_loss_backward(logits, preds, target, m.temp, m.hard_gate, self.lossw)
-                join_branches()
-        finally:
-            self.prepack.invalidate()                # the optimizer below rewrites the weights
-            ops.PREPACK = prev
-            ops.WGRAD_GROUP = prev_group
-        nc = S.clip_grad_norm(self.flat_g, self.clip_val)
-        self.opt.grad_scale_dev = nc[1:2]
-        self.opt.step(None, self.last['total'])
-        self.last['grad_norm'] = nc[0:1]
+        depth = max([len(m.layers) for m in model.modules() if isinstance(m, nn.TransformerEncoder)] or [1])
+        super().__init__(model, lr, weight_decay, clip_val, use_graph, prepack=ops.PackedWeights(), wgrad_group=min(8, depth))
+        self.lossw = float(lossw)
 
-    def __call__(self, inputs, target):
-        if not self.use_graph:
-            self._body(inputs, target)
-            return self.last
+    def _backward(self, inputs, target):
         m = self.model
-        key = (tuple(tuple(x.shape) for x in inputs[0]), float(m.temp), bool(m.hard_gate), bool(m.training))
-        entry = self._graphs.get(key)
-        if entry is None:
-            static_in = [[x.clone() for x in inputs[0]], inputs[1]]
-            static_y = target.clone()
-            snap = [self.flatp.flat.clone()] + [t.clone() for t in self.opt.state_tensors()]
-            self._body(static_in, static_y)                  # warm-up outside capture (allocator, lazy init)
-            self.flatp.flat.copy_(snap[0])                   # undo the warm-up's parameter update
-            for t, c in zip(self.opt.state_tensors(), snap[1:]):
-                t.copy_(c)
-            if self.prepack.reg and self.prepack.dirty:
-                self.prepack._layout()                       # the warm-up registered the weights: lay the arena out before capturing
-            from .. import ops
-            graph = torch.cuda.CUDAGraph()
-            with ops.capture_scope(), torch.cuda.graph(graph):
-                self._body(static_in, static_y)
-            entry = (graph, static_in, static_y, self.last)
-            self._graphs[key] = entry
-        graph, static_in, static_y, static_last = entry
-        for a, b in zip(static_in[0], inputs[0]):
-            a.copy_(b)
-        static_y.copy_(target)
-        graph.replay()
-        self.last = {k: v.clone() for k, v in static_last.items()}
-        return self.last
+        logits, preds = m.gate_and_experts(inputs)
+        last = S.moe_loss_backward(logits, preds, target, m.temp, m.hard_gate, self.lossw)
+        join_branches()
+        return last['total'], last
+
+    def _graph_key(self, inputs, target):
+        m = self.model
+        return (tuple(tuple(x.shape) for x in inputs[0]), float(m.temp), bool(m.hard_gate), bool(m.training))
+
+    def _clone_inputs(self, inputs):
+        return [[x.clone() for x in inputs[0]], inputs[1]]       # (the padding lengths are ignored by the model: kept as they are)
+
+    def _input_tensors(self, inputs):
+        return inputs[0]

@@ -34,7 +34,7 @@ the dense blend up to the GEMMs' fp32 rounding at a different row count.
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import engine, ops
 from .. import ops_mlp as M
 from .. import ops_seq as S
 from .affect import join_branches, run_branches
@@ -250,40 +250,19 @@ class DynMMNet(nn.Module):
         return self.branch3(inputs)
 
 
-class ImdbTrainStep:
-    """One iteration of Supervised_Learning.train's loop for the MM-IMDB DynMM (`moe_model`, additional_loss=True,
-    task "multilabel"): forward, BCEWithLogitsLoss + lossw * gate regulariser, backward, clip_grad_norm_(clip_val), AdamW —
-    flat parameter / gradient / moment buffers, loss and backward seeds and the clip coefficient computed on the device.
+class ImdbTrainStep(engine.FlatAdamWStep):
+    """engine.FlatAdamWStep for the MM-IMDB DynMM (`moe_model`, additional_loss=True, task "multilabel"): BCEWithLogitsLoss +
+    lossw * gate regulariser, with the loss and the backward seeds computed on the device.  Never captured, no prepack.
     Frozen experts (no trainable parameter) run forward only: their BatchNorms still use batch statistics and update their
     running statistics, and their dropouts still drop, as under the reference's model.train()."""
 
     def __init__(self, model, lr=1e-4, weight_decay=1e-2, lossw=0.1, clip_val=8.0):
-        from .. import engine
-        self.model = model
-        params = [p for p in model.parameters() if p.requires_grad]
-        if not params:
-            raise ValueError('ImdbTrainStep: the model has no trainable parameter')
-        self.flatp = engine.FlatParameters(params, align=4)
-        self.flat_g = torch.zeros_like(self.flatp.flat)
-        for p in params:
-            lo, hi = self.flatp.span[id(p)]
-            p.grad = self.flat_g[lo:hi].view_as(p)
-        self.opt = engine.Adam(self.flatp, self.flat_g, lr, weight_decay=weight_decay, decoupled=True)   # AdamW
-        self.lossw, self.clip_val = float(lossw), float(clip_val)
-        self.last = None
+        super().__init__(model, lr, weight_decay, clip_val)
+        self.lossw = float(lossw)
 
-    def __call__(self, inputs, target):
-        from .. import engine
+    def _backward(self, inputs, target):
         m = self.model
-        self.flat_g.zero_()
-        S.advance_dropout_step(self.flat_g.device)     # new dropout masks every step
-        with engine.direct_gradients(False):           # kernels write parameter gradients straight into flat_g
-            ops.touched_reset()
-            logits, preds = m.gate_and_experts(inputs)
-            self.last = M.ml_loss_backward(logits, preds, target, m.temp, m.hard_gate, self.lossw)
-            join_branches()
-        nc = S.clip_grad_norm(self.flat_g, self.clip_val)
-        self.opt.grad_scale_dev = nc[1:2]
-        self.opt.step(None, self.last['total'])
-        self.last['grad_norm'] = nc[0:1]
-        return self.last
+        logits, preds = m.gate_and_experts(inputs)
+        last = M.ml_loss_backward(logits, preds, target, m.temp, m.hard_gate, self.lossw)
+        join_branches()
+        return last['total'], last

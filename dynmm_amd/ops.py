@@ -112,23 +112,10 @@ def _wino(g, dgrad, x2=None, infer=False):
     return ok
 
 
-# Opt-in (TrainStep / bench): when a parameter already owns a contiguous `.grad` buffer (a view into the
-# flat gradient buffer of dp.GradBucketReducer), backward kernels write the parameter gradient
-# STRAIGHT into it and return None to autograd — no temporary, no per-parameter accumulate kernel
-# (607 tiny adds per step).  Semantics: overwrite, so valid for one backward per zero().
-DIRECT_GRAD = False
-
-
-# Opt-in with DIRECT_GRAD: launch every conv weight-gradient kernel on a dedicated stream.  dgrad and
-# wgrad of a layer depend only on the incoming gradient, so the wgrad queue runs concurrently with
-# the main backward chain and fills its ramp-up / tail bubbles.  Tensors it reads are kept alive in
-# _INFLIGHT until join_async() (call it after backward, on the stream that consumes the gradients).
-ASYNC_WGRAD = False
 WGRAD_STREAMS = 2        # weight-gradient side streams.  With the null stream and the depth-encoder stream that makes the FOUR busy
                          # streams the runtime's hardware queues hold: a third one costs 10 ms per step (profiles/r05_ab_runs.md:
                          # 74.5 against 63.7 ms; one stream: 64.6)
 _WGRAD_RR = [0]
-_INFLIGHT = []
 
 
 # ---- the stream plan: a PROCESS-WIDE invariant ----------------------------------------------------------------------------------
@@ -344,39 +331,111 @@ def stream_census(check=True):
     return {'streams': len(_CENSUS), 'roles': roles}
 
 
-def join_async():
-    flush_wgrad_groups()
-    if _INFLIGHT:
-        cur = torch.cuda.current_stream()
-        for s in stream_plan().wgrad:
-            cur.wait_stream(s)
-    _INFLIGHT.clear()
-
-
-# Grouped weight gradients (dynmm_conv2d_wgrad_group): under the in-place gradient protocol a convolution's weight
-# gradient is queued by geometry instead of launched; WGRAD_GROUP same-shape problems (the factorised convs of
-# consecutive residual blocks, RGB and depth encoder alike) go out as ONE launch.  Queues are flushed by join_async()
-# at the end of backward at the latest; the parameters are reported to the gradient reducer when their launch is
-# actually enqueued.
+# ---- the step in flight ---------------------------------------------------------------------------------------------------------
+# The in-place gradient protocol.  Inside step_scope(), when a parameter already owns a contiguous `.grad` buffer (a view into a
+# flat gradient buffer), backward kernels write the parameter gradient STRAIGHT into it and return None to autograd — no
+# temporary, no per-parameter accumulate kernel (607 tiny adds per step).  Semantics: overwrite, so valid for one backward per
+# zero().  Every such backward registers the parameter in the step's `pending` list (via _grad_dst) and, once the kernels that
+# write it are enqueued, calls _grads_enqueued(streams): the parameter joins the step's `touched` set (the flat optimizers update
+# only those ranges, as torch.optim skips parameters whose grad is None) and the step's `on_grad_written` callback — a
+# dp.GradBucketReducer's — learns that the gradient will be complete once the given streams reach this point, so a bucket's
+# all-reduce can start while the rest of backward still runs.  Outside a scope every backward keeps torch's accumulate semantics.
+#
+# Grouped weight gradients (dynmm_conv2d_wgrad_group): a convolution's weight gradient is queued by geometry instead of launched;
+# `wgrad_group` same-shape problems (the factorised convs of consecutive residual blocks, RGB and depth encoder alike) go out as
+# ONE launch.  Queues are flushed when the scope ends at the latest; the parameters are reported when their launch is enqueued.
+#
+# async_wgrad: every conv weight-gradient kernel is launched on a dedicated stream.  dgrad and wgrad of a layer depend only on
+# the incoming gradient, so the wgrad queue runs concurrently with the main backward chain and fills its ramp-up / tail bubbles.
+# The tensors it reads are kept alive in `inflight` until the stream that consumes the gradients has waited for those streams
+# (join_async(); the end of the scope at the latest).
 WGRAD_GROUP = 4
 WGRAD_GROUP_AGE = 4
-_WGRAD_QUEUES = {}
 _CAPTURE_EVENTS = []       # events recorded while a stream capture was in progress (kept alive: see _queue_wgrad)
-_WGRAD_TICK = [0]          # conv backward calls seen; a queue that got nothing for WGRAD_GROUP_AGE of them is flushed
-_WGRAD_LAST = {}           # (the backward has left the run of layers with that geometry: do not hold its gradients back)
+
+
+class Step:
+    """What one training step in flight owns (see step_scope)."""
+
+    def __init__(self, prepack=None, wgrad_group=None, async_wgrad=False, on_grad_written=None):
+        self.prepack = prepack                     # PackedWeights of the step's conv weights, or None
+        self.wgrad_group = max(WGRAD_GROUP, wgrad_group or 0)
+        self.async_wgrad = bool(async_wgrad)
+        self.on_grad_written = on_grad_written     # f(param, streams) or None
+        self.pending = []          # parameters whose .grad view was handed out since the last _grads_enqueued()
+        self.touched = set()       # id() of every parameter whose gradient kernels are enqueued
+        self.queues = {}           # geometry key -> queued weight-gradient problems
+        self.tick = 0              # conv backward calls seen; a queue that got nothing for WGRAD_GROUP_AGE of them is flushed
+        self.queue_tick = {}       # (the backward has left the run of layers with that geometry: do not hold its gradients back)
+        self.inflight = []         # tensors the weight-gradient streams still read
+
+
+_STEP = None       # the step in flight.  A plain module attribute on purpose: autograd runs a device Function's backward on its
+                   # own worker thread, where a thread- or context-local set by the caller is not visible.  Hence ONE step at a
+                   # time per process.
+
+
+@contextlib.contextmanager
+def step_scope(prepack=None, wgrad_group=None, async_wgrad=False, on_grad_written=None):
+    """Make a fresh Step the current one for a forward + backward and yield it.  On entry the prepack (if any) is packed; on
+    exit — also on an exception — queued weight-gradient groups are flushed, the current stream waits for the weight-gradient
+    streams if they still read tensors of this step (which are released only then: the caching allocator must not hand their
+    memory out under a side stream), and the prepack is invalidated (the optimizer rewrites the weights next)."""
+    global _STEP
+    if _STEP is not None:
+        raise L.DynmmHipError('ops.step_scope: a step is already in flight (one step at a time per process)')
+    _STEP = step = Step(prepack, wgrad_group, async_wgrad, on_grad_written)
+    try:
+        if prepack is not None:
+            prepack.pack()
+        yield step
+    finally:
+        try:
+            join_async()
+        finally:
+            if prepack is not None:
+                prepack.invalidate()
+            _STEP = None
+
+
+def in_step():
+    return _STEP is not None
+
+
+def join_async():
+    step = _STEP
+    if step is None:
+        return
+    try:
+        flush_wgrad_groups()
+    finally:
+        if step.inflight:
+            cur = torch.cuda.current_stream()
+            for s in stream_plan().wgrad:
+                cur.wait_stream(s)
+        step.inflight.clear()
 
 
 def _age_wgrad_queues():
-    _WGRAD_TICK[0] += 1
-    if _WGRAD_QUEUES:
-        now = _WGRAD_TICK[0]
-        for key in [k for k in _WGRAD_QUEUES if now - _WGRAD_LAST.get(k, now) > WGRAD_GROUP_AGE]:
-            _flush_wgrad_queue(key)
+    step = _STEP
+    if step is None or step.wgrad_group <= 1:
+        return
+    step.tick += 1
+    for key in [k for k in step.queues if step.tick - step.queue_tick.get(k, step.tick) > WGRAD_GROUP_AGE]:
+        _flush_wgrad_queue(key)
+
+
+def _wgrad_grouped(g, *params):
+    """is the weight gradient of this convolution queued for a grouped launch?  (in-place gradient protocol only: the gradients
+    of `params` go straight into their .grad views)"""
+    return _STEP is not None and _STEP.wgrad_group > 1 and all(_direct_ok(p) for p in params) and \
+        bool(_lib().dynmm_conv2d_wgrad_groupable(C.byref(g)))
 
 
 def _queue_wgrad(g, x, gy, w_param, b_param):
+    step = _STEP
     st = torch.cuda.current_stream()                    # gy is produced on this stream
-    use_async = ASYNC_WGRAD and PROFILE is None
+    use_async = step.async_wgrad and PROFILE is None
     # without the weight-gradient streams a group is launched on the stream its members were produced on: one queue per
     # stream, no events (the branches of the ModalityDynMM step each run on their own stream)
     key = (g.N, g.Ci, g.H, g.W, g.Co, g.KH, g.KW, g.SH, g.SW, g.PH, g.PW, b_param is not None,
@@ -390,22 +449,23 @@ def _queue_wgrad(g, x, gy, w_param, b_param):
             # reference goes (here: when its group is flushed, still inside the capture), and hipStreamEndCapture then
             # intermittently faults on the freed node (seen as a segfault in capture_end, order- and timing-dependent)
             _CAPTURE_EVENTS.append(ev)
-    q = _WGRAD_QUEUES.setdefault(key, [])
+    q = step.queues.setdefault(key, [])
     q.append((g, x, gy, w_param, b_param, ev, st))
-    _WGRAD_LAST[key] = _WGRAD_TICK[0]
-    if len(q) >= WGRAD_GROUP:
+    step.queue_tick[key] = step.tick
+    if len(q) >= step.wgrad_group:
         _flush_wgrad_queue(key)
 
 
 def _flush_wgrad_queue(key):
-    q = _WGRAD_QUEUES.pop(key, None)
-    _WGRAD_LAST.pop(key, None)
+    step = _STEP
+    q = step.queues.pop(key, None) if step is not None else None
     if not q:
         return
+    step.queue_tick.pop(key, None)
     lib = _lib()
     g = q[0][0]
     n = len(q)
-    use_async = ASYNC_WGRAD and PROFILE is None
+    use_async = step.async_wgrad and PROFILE is None
     stream = _wgrad_stream() if use_async else q[0][6]
     for item in q:
         if item[5] is not None:
@@ -413,8 +473,8 @@ def _flush_wgrad_queue(key):
         elif item[6] != stream:
             stream.wait_stream(item[6])
     # parameters registered by the backward that triggered this flush belong to ITS streams: set them aside
-    held = _PENDING[:]
-    del _PENDING[:]
+    held = step.pending[:]
+    del step.pending[:]
     dws = [_grad_dst(item[3])[0] for item in q]
     dbs = [_grad_dst(item[4])[0] for item in q] if q[0][4] is not None else None
     nbytes = lib.dynmm_conv2d_wgrad_group_workspace_bytes(C.byref(g), n)
@@ -433,47 +493,27 @@ def _flush_wgrad_queue(key):
         else:
             L.check(call(), 'conv2d_wgrad_group')
     if use_async:
-        _INFLIGHT.append(tuple(t for item in q for t in (item[1], item[2])))
+        step.inflight.append(tuple(t for item in q for t in (item[1], item[2])))
     _grads_enqueued(stream)
-    _PENDING.extend(held)
+    step.pending.extend(held)
 
 
 def flush_wgrad_groups():
-    for key in list(_WGRAD_QUEUES):
-        _flush_wgrad_queue(key)
-
-
-# Bookkeeping of the in-place gradient protocol.  Every backward that writes a parameter gradient straight
-# into its `.grad` view registers the parameter in _PENDING (via _grad_dst) and, once the kernels that write
-# it are enqueued, calls _grads_enqueued(streams): the parameter joins the set of parameters touched in this
-# step (the flat optimizers update only those ranges, as torch.optim skips parameters whose grad is None) and
-# GRAD_READY_HOOK — installed by dp.GradBucketReducer — learns that the gradient will be complete once the
-# given streams reach this point, so a bucket's all-reduce can start while the rest of backward still runs.
-GRAD_READY_HOOK = None
-_PENDING = []
-_TOUCHED = set()
-
-
-def touched_reset():
-    _TOUCHED.clear()
-    _PENDING.clear()
-
-
-def touched_ids():
-    return frozenset(_TOUCHED)
+    if _STEP is not None:
+        for key in list(_STEP.queues):
+            _flush_wgrad_queue(key)
 
 
 def _direct_ok(param):
     """_grad_dst(param) would hand out the parameter's own .grad view"""
-    return DIRECT_GRAD and param is not None and getattr(param, 'grad', None) is not None and \
+    return _STEP is not None and param is not None and getattr(param, 'grad', None) is not None and \
         param.grad.is_contiguous() and param.grad.dtype == torch.float32
 
 
 def _grad_dst(param, like=None):
     """(tensor to write the gradient into, value to return to autograd)."""
-    if DIRECT_GRAD and param is not None and getattr(param, 'grad', None) is not None and param.grad.is_contiguous() \
-            and param.grad.dtype == torch.float32:
-        _PENDING.append(param)
+    if _direct_ok(param):
+        _STEP.pending.append(param)
         return param.grad, None
     t = torch.empty_like(param if like is None else like)
     return t, t
@@ -482,16 +522,15 @@ def _grad_dst(param, like=None):
 def _grads_enqueued(*streams):
     """The kernels writing the gradients handed out by _grad_dst since the last call are enqueued on `streams`
     (default: the current stream)."""
-    if not _PENDING:
+    step = _STEP
+    if step is None or not step.pending:
         return
-    hook = GRAD_READY_HOOK
-    if hook is not None:
+    if step.on_grad_written is not None:
         ss = [s for s in streams if s is not None] or [torch.cuda.current_stream()]
-        for prm in _PENDING:
-            hook(prm, ss)
-    for prm in _PENDING:
-        _TOUCHED.add(id(prm))
-    _PENDING.clear()
+        for prm in step.pending:
+            step.on_grad_written(prm, ss)
+    step.touched.update(id(prm) for prm in step.pending)
+    step.pending.clear()
 
 
 @contextlib.contextmanager
@@ -651,7 +690,7 @@ BN_RELU_BITS = True
 class PackedWeights:
     """The operand layouts of every conv weight a training step uses — the implicit-GEMM layouts (dynmm_pack_weight) and the
     Winograd filter transforms (dynmm_wino_pack) — produced by ONE launch each per step instead of one per convolution (186
-    for config P).  engine.TrainStep installs an instance as ops.PREPACK: the first step runs the ordinary per-conv packs
+    for config P).  A training step hands an instance to ops.step_scope(prepack=...): the first step runs the ordinary per-conv packs
     and registers (weight, shape, which of the four operands its passes read); from then on pack() fills a static arena at
     the start of the step body and the convolutions look their operands up.  Entries are valid between pack() and
     invalidate() only (the optimizer rewrites the weights after the body)."""
@@ -780,9 +819,6 @@ class PackedWeights:
         self.valid = False
 
 
-PREPACK = None
-
-
 class _Conv2d(Function):
     @staticmethod
     def forward(ctx, x, x2, weight, bias, stride, padding, act, mask_input, defer_mask, link, w_owner=None, stats=None,
@@ -804,7 +840,8 @@ class _Conv2d(Function):
         # (a Linear / Conv1d weight arrives as a [Co, Ci, 1, 1] alias of its parameter: same memory, so the parameter keys the pack)
         wkey = w_owner if w_owner is not None else weight
         wp = wpd = utf = utd = utd43 = ut2f = ut2d = None
-        pre = PREPACK.lookup(wkey, need_wp, need_wpd, wino_f, wino_d, wino_d43, w2f, w2d) if PREPACK is not None else None
+        prepack = _STEP.prepack if _STEP is not None else None
+        pre = prepack.lookup(wkey, need_wp, need_wpd, wino_f, wino_d, wino_d43, w2f, w2d) if prepack is not None else None
         if pre is not None:
             wp, wpd, utf, utd, utd43, ut2f, ut2d = pre           # packed by the step's multi-tensor launches
         else:
@@ -832,8 +869,8 @@ class _Conv2d(Function):
                 if w2d:
                     ut2d = torch.empty(nu2, device=x.device, dtype=torch.float32)
                     L.check(lib.dynmm_wino2d_pack(_p(weight), _p(ut2d), None, g.Co, g.Ci, 1, st), 'wino2d_pack')
-            if PREPACK is not None:
-                PREPACK.register(wkey, g, need_wp, need_wpd, wino_f, wino_d, wino_d43, w2f, w2d)
+            if prepack is not None:
+                prepack.register(wkey, g, need_wp, need_wpd, wino_f, wino_d, wino_d43, w2f, w2d)
         if w2f:
             sums, ns = None, 0
             if stats is not None and act == L.ACT_NONE and g.Co % 64 == 0:
@@ -902,9 +939,8 @@ class _Conv2d(Function):
         # which stages every gy tile anyway; only when the weights take no gradient does it need its own pass.
         bias_in_wgrad = ctx.has_bias and ctx.needs_input_grad[2]
         # queued for a grouped launch (in-place gradient protocol only: the gradients go straight into .grad views)
-        defer = (ctx.needs_input_grad[2] and DIRECT_GRAD and WGRAD_GROUP > 1 and x2 is None and
-                 _direct_ok(ctx.w_param) and (not ctx.has_bias or _direct_ok(ctx.b_param)) and
-                 bool(lib.dynmm_conv2d_wgrad_groupable(C.byref(g))))
+        defer = (ctx.needs_input_grad[2] and x2 is None and
+                 _wgrad_grouped(g, ctx.w_param, *([ctx.b_param] if ctx.has_bias else [])))
         if ctx.has_bias and not (defer and bias_in_wgrad):
             dbias, dbias_ret = _grad_dst(ctx.b_param)
         if act != L.ACT_NONE or (ctx.has_bias and not bias_in_wgrad):
@@ -970,14 +1006,13 @@ class _Conv2d(Function):
                                                                           _p(dx2), C.byref(g), st), extra=extra), 'conv2d_dgrad')
         dw_ret = None
         ws_stream = None
-        if DIRECT_GRAD and WGRAD_GROUP > 1:
-            _age_wgrad_queues()
+        _age_wgrad_queues()
         if defer:
             _queue_wgrad(g, x, gy, ctx.w_param, ctx.b_param if bias_in_wgrad else None)
         elif ctx.needs_input_grad[2]:
             dw, dw_ret = _grad_dst(ctx.w_param)
             nbytes = lib.dynmm_conv2d_wgrad_workspace_bytes(C.byref(g))
-            if ASYNC_WGRAD and dw_ret is None and PROFILE is None:
+            if dw_ret is None and _STEP.async_wgrad and PROFILE is None:
                 ws_stream = _wgrad_stream()
                 _CENSUS.add(ws_stream.cuda_stream)
                 ws_stream.wait_stream(torch.cuda.current_stream())
@@ -985,7 +1020,7 @@ class _Conv2d(Function):
                     ws = torch.empty(max(nbytes // 4, 1), device=gy.device, dtype=torch.float32)
                     L.check(lib.dynmm_conv2d_wgrad(_p(x), _p(x2), _p(gy), _p(dw), _p(dbias) if bias_in_wgrad else None,
                                                    _p(ws), nbytes, C.byref(g), ws_stream.cuda_stream), 'conv2d_wgrad')
-                _INFLIGHT.append((x, x2, gy))
+                _STEP.inflight.append((x, x2, gy))
             else:
                 ws = torch.empty(max(nbytes // 4, 1), device=gy.device, dtype=torch.float32)
                 L.check(_timed('wgrad', g, lambda: lib.dynmm_conv2d_wgrad(_p(x), _p(x2), _p(gy), _p(dw),

@@ -210,8 +210,7 @@ def _wgrad_1x1(x3, gy3, w_param, b_param):
     B, Ci, T = x3.shape
     Co = gy3.shape[1]
     g = L.ConvGeom(B, Ci, 1, T, Co, 1, T, 1, 1, 1, 1, 0, 0, Ci)
-    if (ops.DIRECT_GRAD and ops.WGRAD_GROUP > 1 and ops._direct_ok(w_param) and ops._direct_ok(b_param) and
-            bool(lib.dynmm_conv2d_wgrad_groupable(C.byref(g)))):
+    if ops._wgrad_grouped(g, w_param, b_param):
         ops._queue_wgrad(g, x3, gy3, w_param, b_param)
         return None, None
     dw, dw_ret = _grad_dst(w_param)

@@ -305,7 +305,7 @@ def test_residual_gradient_link_equals_autograd_accumulation(B, D, T, p):
     """An encoder layer's input feeds in_proj and norm1's residual input; with LINK_RESIDUAL norm1's backward hands the residual
     branch's gradient to in_proj's input-gradient epilogue (ops.GradLink) instead of autograd's add pass: same output, input
     gradient and parameter gradients, under plain autograd and under the in-place gradient protocol."""
-    from dynmm_amd import engine, ops, ops_seq as S
+    from dynmm_amd import ops, ops_seq as S
     from dynmm_amd.nn import affect as A
     torch.manual_seed(7 * B + D)
     layer = torch.nn.TransformerEncoderLayer(d_model=D, nhead=5, dim_feedforward=64, dropout=p).cuda().train()
@@ -322,8 +322,7 @@ def test_residual_gradient_link_equals_autograd_accumulation(B, D, T, p):
         try:
             h = h0 * pre
             if direct:
-                with engine.direct_gradients(False):
-                    ops.touched_reset()
+                with ops.step_scope(async_wgrad=False):
                     y = A.encoder_layer(h, layer, 5)
                     y.backward(gy)
                     ops.flush_wgrad_groups()
@@ -351,7 +350,7 @@ def test_fused_feed_forward_block_equals_the_layer_by_layer_path(B, D, T, F, hea
     one launch for both data gradients) against the same encoder layer run as separate linear / dropout / LayerNorm launches,
     with the same injected keep flags: output, input gradient, every parameter gradient — under plain autograd and under the
     in-place gradient protocol of the training step (queued weight gradients)."""
-    from dynmm_amd import engine, ops, ops_seq as S
+    from dynmm_amd import ops, ops_seq as S
     from dynmm_amd.nn import affect as A
     torch.manual_seed(B * 1000 + D)
     layer = torch.nn.TransformerEncoderLayer(d_model=D, nhead=heads, dim_feedforward=F, dropout=p).cuda().train()
@@ -368,8 +367,7 @@ def test_fused_feed_forward_block_equals_the_layer_by_layer_path(B, D, T, F, hea
         h = h0.clone().requires_grad_(True)
         try:
             if direct:
-                with engine.direct_gradients(False):
-                    ops.touched_reset()
+                with ops.step_scope(async_wgrad=False):
                     y = A.encoder_layer(h, layer, heads)
                     y.backward(gy)
                     ops.flush_wgrad_groups()

@@ -144,6 +144,73 @@ def test_uneven_touch_sets_keep_bucket_order_and_share_the_nan():
     assert all(np.array_equal(a, b) for a, b in zip(res[0][1], res[1][1]))
 
 
+class _FakeStream:
+    cuda_stream = 0
+
+
+def _worker_two_reducers(rank, world, port, q):
+    """Two reducers in one process, A built first: each is told about the gradients written in ITS step's scope (the callback
+    belongs to the step, not to the process: the reducer built last used to take the one slot and A's overlap was gone)."""
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    from dynmm_amd import dp, ops
+    from dynmm_amd.lib import DynmmHipError
+    models = [_model(), _model()]
+    reds = [dp.GradBucketReducer(m.parameters(), bucket_mb=0.00001, overlap=True) for m in models]      # A first, then B
+    out = []
+    for k, (m, red) in enumerate(zip(models, reds)):
+        assert len(red.buckets) > 1
+        red.zero()
+        with ops.step_scope(on_grad_written=red._on_grad_written) as step:
+            for i, p in enumerate(reversed(list(m.parameters()))):
+                dst, ret = ops._grad_dst(p)
+                assert ret is None and dst.data_ptr() == p.grad.data_ptr()
+                dst.fill_(float((rank + 1) * (10 * k + i + 1)))
+                ops._grads_enqueued(_FakeStream())
+            touched = len(step.touched)
+        in_bwd = red.launched_in_backward
+        red.finish(average=False)
+        out.append((in_bwd, len(red.buckets), touched, [p.grad.numpy().copy() for p in reversed(list(m.parameters()))]))
+    # one step at a time; the scope ends (and the prepack is invalid) also after an exception
+    nested = False
+    pw = ops.PackedWeights()
+    try:
+        with ops.step_scope(prepack=pw):
+            pw.valid = True
+            try:
+                with ops.step_scope():
+                    pass
+            except DynmmHipError:
+                nested = True
+            assert ops._STEP is not None and ops._STEP.prepack is pw        # the refused scope left the outer one in place
+            raise KeyError('inside the scope')
+    except KeyError:
+        pass
+    q.put((rank, out, nested, ops._STEP is None, pw.valid))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_gradient_written_callback_belongs_to_the_step_not_the_process():
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_two_reducers, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=120) for _ in range(2)], key=lambda t: t[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for rank, out, nested, step_gone, prepack_valid in res:
+        assert nested and step_gone and not prepack_valid, (rank, nested, step_gone, prepack_valid)
+        for k, (in_bwd, nb, touched, grads) in enumerate(out):
+            assert in_bwd == nb, (rank, k, in_bwd, nb)                 # every bucket of A AND of B went out "during backward"
+            assert touched == len(grads)
+            for i, g in enumerate(grads):
+                assert np.array_equal(g, np.full_like(g, 3.0 * (10 * k + i + 1))), (rank, k, i)     # (1 + 2) x: the sum over ranks
+
+
 def test_shard_batch_partitions():
     from dynmm_amd import dp
     for n, w in ((256, 8), (10, 4), (3, 8)):

@@ -2,7 +2,7 @@
 gradients over gloo (the driver's 8-GPU RCCL run is not ours to launch; the code path — flat buffer, buckets,
 in-place gradient protocol, overlap hooks, side-stream waits, fused optimizer on the averaged buffer — is the
 one `bench.py --gpus N` / train.py use over RCCL).  Checks, bit for bit:
-  * every bucket's all-reduce is launched DURING backward (overlap with ops.DIRECT_GRAD),
+  * every bucket's all-reduce is launched DURING backward (overlap with the in-place gradient protocol of ops.step_scope),
   * the reduced flat gradient is identical on both ranks and equals (g_rank0 + g_rank1) / 2 of the
     un-reduced per-rank gradients,
   * after the fused SGD step both replicas hold identical parameters."""

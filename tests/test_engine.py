@@ -460,7 +460,7 @@ def test_prepacked_weights_step_is_bit_identical(monkeypatch):
         torch.cuda.synchronize()
         if pre:
             assert len(step.prepack.reg) > 150 and step.prepack.arena is not None and not step.prepack.valid
-            assert ops.PREPACK is None
+            assert ops._STEP is None
         res[pre] = (losses, {k: v.detach().cpu().clone() for k, v in m.state_dict().items()},
                     {k: p.grad.detach().cpu().clone() for k, p in m.named_parameters()})
     assert res[True][0] == res[False][0]
@@ -599,6 +599,48 @@ def test_stream_plan_is_process_wide_three_models_in_sequence():
         del m, ts
         torch.cuda.empty_cache()
     assert max(times) / min(times) < 1.03, times
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('graph_on', [None, 'P_se'])
+def test_two_train_steps_in_one_process_do_not_disturb_each_other(graph_on):
+    """The state of a step in flight (prepack, weight-gradient queues, touched set, in-flight references) lives in the step's own
+    ops.step_scope: two models of different configuration stepped alternately A, B, A, B, A, B on the 4-stream schedule end bit
+    for bit where the same model ends when stepped three times alone from the same initial state in a fresh TrainStep —
+    parameters, gradients, BatchNorm running statistics and the last total loss.  Second leg: one of the two replays a hipGraph."""
+    from dynmm_amd import engine
+    from tests.test_hip_model import hip_model
+    h, w, cw = 96, 128, np.linspace(0.5, 2.0, 40)
+    rgb, depth, labels = _batch(4, h, w)
+    seeds = {'P_se': 1, 'S_add': 2}
+
+    def run(order):
+        steps, last = {}, {}
+        for cfg in dict.fromkeys(order):
+            m = hip_model(cfg, h, w, seed=seeds[cfg]).train()
+            m.temp, m.hard_gate = 1.0, False
+            steps[cfg] = engine.TrainStep(m, cw, lr=0.01, loss_ratio=0.1, multi_stream=True, use_graph=cfg == graph_on)
+        for cfg in order:
+            last[cfg] = steps[cfg](rgb, depth, labels)['total'].clone()
+        torch.cuda.synchronize()
+        out = {}
+        for cfg, ts in steps.items():
+            assert ts.use_graph == (cfg == graph_on) and len(ts._graphs) == int(ts.use_graph)
+            ts.opt.check_finite()
+            bn = {k: v.clone() for k, v in ts.model.state_dict().items() if 'running_' in k}
+            assert bn
+            out[cfg] = (ts.flatp.flat.clone(), ts.reducer.flat.clone(), bn, last[cfg])
+        return out
+
+    both = run(['P_se', 'S_add'] * 3)
+    for cfg in seeds:
+        alone = run([cfg] * 3)[cfg]
+        flat, grads, bn, total = both[cfg]
+        assert torch.equal(flat, alone[0]), cfg
+        assert torch.equal(grads, alone[1]) and grads.abs().max() > 0, cfg
+        for k, v in bn.items():
+            assert torch.equal(v, alone[2][k]), (cfg, k)
+        assert torch.equal(total, alone[3]), (cfg, total, alone[3])
 
 
 @pytest.mark.gpu

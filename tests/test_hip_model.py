@@ -452,7 +452,7 @@ def test_all_parameter_gradients_are_run_to_run_reproducible(dual):
     same way).  Their order noise is ~1e-16 relative and is rounded away when mean / invstd / dgamma / dbeta are formed in fp32
     (a change needs the fp64 value within 1e-16 of an fp32 rounding boundary: ~1e-9 per value) — bit-identical here, and at the
     size where tiles number in the thousands in test_full_size_gradients_are_run_to_run_reproducible below."""
-    from dynmm_amd import engine
+    from dynmm_amd import ops
     h, w, n = 96, 128, 4
     rgb, depth = synth.synth_inputs(n, h, w, seed=5, device='cuda')
     grads = []
@@ -462,10 +462,9 @@ def test_all_parameter_gradients_are_run_to_run_reproducible(dual):
         m.temp, m.dual_stream = 0.7, dual
         for p in m.parameters():
             p.grad = torch.zeros_like(p)
-        with engine.direct_gradients(dual):
+        with ops.step_scope(async_wgrad=dual):
             outs, lf = m(rgb, depth)
             Hh.train_loss(outs, lf).backward()
-            from dynmm_amd import ops
             ops.join_async()
         torch.cuda.synchronize()
         grads.append({k: p.grad.clone() for k, p in m.named_parameters()})
@@ -480,7 +479,7 @@ def test_full_size_gradients_are_run_to_run_reproducible():
     train step from the same state.  fp64-atomic order is the ONE tolerated source of run-to-run difference on this path (see
     above); it is bounded here: every parameter gradient within 1e-6 in relative L2 of the first run's — in practice
     bit-identical, the count of tensors that are not is printed."""
-    from dynmm_amd import engine, ops
+    from dynmm_amd import ops
     h, w, n = 480, 640, 32
     rgb, depth = synth.synth_inputs(n, h, w, seed=5, device='cuda')
     m = hip_model('P_se', h, w, seed=1)
@@ -492,7 +491,7 @@ def test_full_size_gradients_are_run_to_run_reproducible():
     for _ in range(2):
         for p in m.parameters():
             p.grad.zero_()
-        with engine.direct_gradients(True):
+        with ops.step_scope(async_wgrad=True):
             outs, lf = m(rgb, depth)
             Hh.train_loss(outs, lf).backward()
             ops.join_async()
