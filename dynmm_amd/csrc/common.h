@@ -62,19 +62,44 @@ __device__ __forceinline__ T block_reduce_sum_256(T v, T* smem) {
     return r;
 }
 
+// Swish z * sigmoid(z) and Hswish z * relu6(z + 3) / 6 (model_utils.py:100-115), in the reference's order of operations.
+// (z -> -inf: expf(-z) = +inf, the quotient is -0: finite, no NaN.)
+__device__ __forceinline__ float swish_fwd(float v) { return v / (1.f + expf(-v)); }
+__device__ __forceinline__ float hswish_fwd(float v) { return v * fminf(fmaxf(v + 3.f, 0.f), 6.f) / 6.f; }
+
 __device__ __forceinline__ float act_fwd(float v, int act) {
     if (act == DYNMM_ACT_RELU) return v > 0.f ? v : 0.f;
     if (act == DYNMM_ACT_TANH) return tanhf(v);
+    if (act == DYNMM_ACT_SWISH) return swish_fwd(v);
+    if (act == DYNMM_ACT_HSWISH) return hswish_fwd(v);
     return v;
 }
 
+// derivative of the activation at the PRE-activation z: the only form Swish and Hswish have (neither is invertible — minima
+// near -1.28 and at -1.5).  Hswish follows torch's autograd at the kinks: hardtanh's gradient mask is strict, so the middle
+// segment is -3 < z < 3 — at exactly z = 3 the derivative is 1, at exactly z = -3 it is 0.
+__device__ __forceinline__ float act_grad_pre(float z, int act) {
+    if (act == DYNMM_ACT_RELU) return z > 0.f ? 1.f : 0.f;
+    if (act == DYNMM_ACT_TANH) { const float t = tanhf(z); return 1.f - t * t; }
+    if (act == DYNMM_ACT_SWISH) {
+        const float s = 1.f / (1.f + expf(-z));
+        return s * (1.f + z * (1.f - s));
+    }
+    if (act == DYNMM_ACT_HSWISH) return z <= -3.f ? 0.f : (z < 3.f ? (2.f * z + 3.f) / 6.f : 1.f);
+    return 1.f;
+}
+
 // derivative of the activation expressed through its OUTPUT y (ReLU: y>0, tanh: 1-y^2), so the
-// backward never needs the pre-activation tensor (SURVEY.md §7 "shared in-place ReLU").
+// backward never needs the pre-activation tensor (SURVEY.md §7 "shared in-place ReLU").  ReLU and tanh ONLY: the entry points
+// that use it refuse the smooth codes (act_is_smooth), whose backward goes through act_grad_pre.
 __device__ __forceinline__ float act_bwd(float g, float y, int act) {
     if (act == DYNMM_ACT_RELU) return y > 0.f ? g : 0.f;
     if (act == DYNMM_ACT_TANH) return g * (1.f - y * y);
     return g;
 }
+
+static inline bool act_is_smooth(int act) { return act == DYNMM_ACT_SWISH || act == DYNMM_ACT_HSWISH; }
+static inline bool act_is_known(int act) { return act >= DYNMM_ACT_NONE && act <= DYNMM_ACT_HSWISH; }
 
 // out[i] = sum_s slabs[s][i] (+ an optional second region) in a fixed order: the deterministic tail of every
 // split reduction in the library (conv_igemm.hip).

@@ -381,6 +381,12 @@ __global__ void __launch_bounds__(256, (TCO * TPIX > 8192 ? 2 : (TPIX > 128 ? 4 
             } else if (act == DYNMM_ACT_TANH) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = tanhf(v[j]);
+            } else if (act == DYNMM_ACT_SWISH) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = swish_fwd(v[j]);
+            } else if (act == DYNMM_ACT_HSWISH) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = hswish_fwd(v[j]);
             }
         }
     };
@@ -1426,6 +1432,7 @@ extern "C" int dynmm_conv2d_fwd(const float* x, const float* x2, const float* wp
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
     if (!x || !wp_fwd || !y || !geom_ok(g)) return DYNMM_EINVAL;
     if ((g->c_split < g->Ci) != (x2 != nullptr)) return DYNMM_EINVAL;
+    if (!act_is_known(act)) return DYNMM_EINVAL;
     IgemmArgs a{};
     a.x = x; a.x2 = x2; a.wp = wp_fwd; a.scale = scale; a.shift = shift; a.residual = residual;
     a.mask = nullptr; a.y = y; a.y2 = nullptr;

@@ -318,6 +318,12 @@ __global__ void __launch_bounds__(256, 3) conv_igemm_v5_kernel(const IgemmArgs a
             } else if (act == DYNMM_ACT_TANH) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = tanhf(v[j]);
+            } else if (act == DYNMM_ACT_SWISH) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = swish_fwd(v[j]);
+            } else if (act == DYNMM_ACT_HSWISH) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = hswish_fwd(v[j]);
             }
         }
     };

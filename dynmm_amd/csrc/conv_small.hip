@@ -25,6 +25,8 @@ constexpr int kSCols = kSColGroups * kSP;      // 80 output columns per workgrou
 __device__ __forceinline__ float small_act(float v, int act) {
     if (act == DYNMM_ACT_RELU) return v > 0.f ? v : 0.f;
     if (act == DYNMM_ACT_TANH) return tanhf(v);
+    if (act == DYNMM_ACT_SWISH) return swish_fwd(v);          // (common.h: the same two functions act_fwd uses)
+    if (act == DYNMM_ACT_HSWISH) return hswish_fwd(v);
     return v;
 }
 
@@ -491,8 +493,11 @@ __global__ void __launch_bounds__(256, CI == 1 ? 3 : 2) conv_stem_fwd_kernel(con
                     const int cl = (jj & 3) + 8 * (jj >> 2) + 4 * khalf;
                     const int c = mi * 32 + 16 * q + cl;
                     const float sc = a.scale ? a.scale[c] : 1.f, sh = a.shift ? a.shift[c] : 0.f;
-                    ostage[cl * OP + l31] = small_act(fmaf(acc[rr][0][j], sc, sh), a.act);
-                    ostage[cl * OP + 32 + l31] = small_act(fmaf(acc[rr][1][j], sc, sh), a.act);
+                    // (STATS instances run with act = NONE only — launch_stem refuses anything else — and carry no activation
+                    //  code at all: with the Swish exp in it, conv_stem_fwd_kernel<1,true> went over its scratch budget)
+                    const int act = STATS ? DYNMM_ACT_NONE : a.act;
+                    ostage[cl * OP + l31] = small_act(fmaf(acc[rr][0][j], sc, sh), act);
+                    ostage[cl * OP + 32 + l31] = small_act(fmaf(acc[rr][1][j], sc, sh), act);
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();

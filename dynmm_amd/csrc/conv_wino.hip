@@ -497,6 +497,12 @@ __global__ void __launch_bounds__(256, MCO == 1 ? ((VERT && !DGRAD) ? 4 : 3) : 2
                 } else if (act == DYNMM_ACT_TANH) {
                     y0 = tanhf(y0);
                     y1 = tanhf(y1);
+                } else if (act == DYNMM_ACT_SWISH) {
+                    y0 = swish_fwd(y0);
+                    y1 = swish_fwd(y1);
+                } else if (act == DYNMM_ACT_HSWISH) {
+                    y0 = hswish_fwd(y0);
+                    y1 = hswish_fwd(y1);
                 }
             }
             v0[e] = y0;
@@ -739,6 +745,7 @@ extern "C" int dynmm_conv2d_wino_fwd(const float* x, const float* ut, const floa
                                      const dynmm_conv_geom* g, int act, void* stream) {
     (void)hipGetLastError();
     if (!x || !ut || !y || !g) return DYNMM_EINVAL;
+    if (!act_is_known(act)) return DYNMM_EINVAL;
     if (!wino_geom_ok(g, false)) return DYNMM_EUNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual)) & 7u) return DYNMM_EUNSUPPORTED;

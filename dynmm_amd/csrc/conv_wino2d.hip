@@ -306,6 +306,10 @@ __global__ void __launch_bounds__(256, 2) conv_wino2d_kernel(const Wino2dArgs a)
                     y10 = y10 > 0.f ? y10 : 0.f; y11 = y11 > 0.f ? y11 : 0.f;
                 } else if (a.act == DYNMM_ACT_TANH) {
                     y00 = tanhf(y00); y01 = tanhf(y01); y10 = tanhf(y10); y11 = tanhf(y11);
+                } else if (a.act == DYNMM_ACT_SWISH) {
+                    y00 = swish_fwd(y00); y01 = swish_fwd(y01); y10 = swish_fwd(y10); y11 = swish_fwd(y11);
+                } else if (a.act == DYNMM_ACT_HSWISH) {
+                    y00 = hswish_fwd(y00); y01 = hswish_fwd(y01); y10 = hswish_fwd(y10); y11 = hswish_fwd(y11);
                 }
             }
             if (live) {
@@ -466,6 +470,7 @@ extern "C" int dynmm_conv2d_wino2d_fwd(const float* x, const float* ut, const fl
                                        double* stats, int nslots, const dynmm_conv_geom* g, int act, void* stream) {
     (void)hipGetLastError();
     if (!x || !ut || !y || !g) return DYNMM_EINVAL;
+    if (!act_is_known(act)) return DYNMM_EINVAL;
     if (!wino2d_geom_ok(g, false)) return DYNMM_EUNSUPPORTED;
     if (stats && (g->Co % 64 != 0 || residual || act != DYNMM_ACT_NONE || nslots < 1 || nslots > 64)) return DYNMM_EUNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;

@@ -14,15 +14,16 @@ struct SeParams { const float* p[8]; };   // W1r b1r W2r b2r W1d b1d W2d b2d
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
-// one modality: s[C] (LDS) -> h[Hd] (LDS, also saved) -> g[C] (saved)
+// one modality: s[C] (LDS) -> h[Hd] (LDS, also saved) -> g[C] (saved).  `act` = the hidden activation: ReLU saves the hidden
+// POST-activation (its backward tests h > 0), the smooth codes save the PRE-activation, which their derivative needs.
 __device__ void se_mlp_fwd(const float* s, const float* W1, const float* b1, const float* W2,
-                           const float* b2, float* h_lds, float* h_out, float* g_out, int C, int Hd) {
+                           const float* b2, float* h_lds, float* h_out, float* g_out, int C, int Hd, int act) {
     for (int j = threadIdx.x; j < Hd; j += blockDim.x) {
         float acc = b1[j];
         for (int c = 0; c < C; ++c) acc += W1[j * C + c] * s[c];
-        acc = acc > 0.f ? acc : 0.f;
-        h_lds[j] = acc;
-        h_out[j] = acc;
+        const float hv = act == DYNMM_ACT_RELU ? (acc > 0.f ? acc : 0.f) : act_fwd(acc, act);
+        h_lds[j] = hv;
+        h_out[j] = act == DYNMM_ACT_RELU ? hv : acc;
     }
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
@@ -37,7 +38,7 @@ __global__ void __launch_bounds__(256) se_coeff_fwd_kernel(
     const float* __restrict__ sr, const float* __restrict__ sd, SeParams P,
     const float* __restrict__ wc, int wc_stride, float* __restrict__ a, float* __restrict__ b,
     float* __restrict__ hr, float* __restrict__ hd, float* __restrict__ gr, float* __restrict__ gd,
-    int C, int use_se) {
+    int C, int use_se, int act) {
     __shared__ float s_lds[kMaxC];
     __shared__ float h_lds[kMaxHid];
     const int n = blockIdx.x;
@@ -46,10 +47,10 @@ __global__ void __launch_bounds__(256) se_coeff_fwd_kernel(
     if (use_se) {
         for (int c = threadIdx.x; c < C; c += blockDim.x) s_lds[c] = sr[(size_t)n * C + c];
         __syncthreads();
-        se_mlp_fwd(s_lds, P.p[0], P.p[1], P.p[2], P.p[3], h_lds, hr + (size_t)n * Hd, gr + (size_t)n * C, C, Hd);
+        se_mlp_fwd(s_lds, P.p[0], P.p[1], P.p[2], P.p[3], h_lds, hr + (size_t)n * Hd, gr + (size_t)n * C, C, Hd, act);
         for (int c = threadIdx.x; c < C; c += blockDim.x) s_lds[c] = sd[(size_t)n * C + c];
         __syncthreads();
-        se_mlp_fwd(s_lds, P.p[4], P.p[5], P.p[6], P.p[7], h_lds, hd + (size_t)n * Hd, gd + (size_t)n * C, C, Hd);
+        se_mlp_fwd(s_lds, P.p[4], P.p[5], P.p[6], P.p[7], h_lds, hd + (size_t)n * Hd, gd + (size_t)n * C, C, Hd, act);
     }
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const float g_r = use_se ? gr[(size_t)n * C + c] : 1.f;
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(256) se_coeff_fwd_kernel(
 // are formed by mlp_param_grad_kernel in a fixed sample order (no float atomics => bit-reproducible).
 __device__ void se_mlp_bwd(const float* dg, const float* h, const float* g, const float* W1, const float* W2,
                            float* dz2_lds, float* dh_lds, float* dz2_out, float* dh_out, float* ds_out,
-                           int C, int Hd) {
+                           int C, int Hd, int act) {
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const float gg = g[c];
         const float dz = dg[c] * gg * (1.f - gg);
@@ -77,7 +78,8 @@ __device__ void se_mlp_bwd(const float* dg, const float* h, const float* g, cons
     for (int j = threadIdx.x; j < Hd; j += blockDim.x) {
         float acc = 0.f;
         for (int c = 0; c < C; ++c) acc += W2[c * Hd + j] * dz2_lds[c];
-        acc = h[j] > 0.f ? acc : 0.f;
+        // (h: the hidden post-activation for ReLU, the pre-activation otherwise — se_mlp_fwd)
+        acc = act == DYNMM_ACT_RELU ? (h[j] > 0.f ? acc : 0.f) : acc * act_grad_pre(h[j], act);
         dh_lds[j] = acc;
         dh_out[j] = acc;
     }
@@ -95,7 +97,7 @@ __device__ void se_mlp_bwd(const float* dg, const float* h, const float* g, cons
 //   dW2[c][j] = sum_n dz[n][c] h[n][j]   db2[c] = sum_n dz[n][c]          (n ascending: deterministic)
 struct MlpGradJob {
     const float* s;    // [N][C]  layer-1 input (pooled features)
-    const float* h;    // [N][Hd] layer-1 output (post-ReLU)
+    const float* h;    // [N][Hd] layer-1 output as se_mlp_fwd saved it (post-ReLU; pre-activation for the smooth codes)
     const float* dz;   // [N][C]  scratch
     const float* dh;   // [N][Hd] scratch
     float* dW1; float* db1; float* dW2; float* db2;
@@ -104,7 +106,7 @@ struct MlpGradJob {
 };
 struct MlpGradJobs { MlpGradJob j[2]; };
 
-__global__ void __launch_bounds__(256) mlp_param_grad_kernel(MlpGradJobs jobs, int N, int C, int Hd) {
+__global__ void __launch_bounds__(256) mlp_param_grad_kernel(MlpGradJobs jobs, int N, int C, int Hd, int act) {
     const MlpGradJob J = jobs.j[blockIdx.y];
     const int e0 = blockIdx.x * 256 + threadIdx.x;
     const int nW = Hd * C;
@@ -134,7 +136,11 @@ __global__ void __launch_bounds__(256) mlp_param_grad_kernel(MlpGradJobs jobs, i
     if (e < nW) {                                    // dW2[c][j]
         const int c = e / Hd, j = e - c * Hd;
         float acc = 0.f;
-        for (int n = 0; n < N; ++n) acc += J.dz[(size_t)n * C + c] * J.h[(size_t)n * Hd + j];
+        if (act == DYNMM_ACT_RELU) {
+            for (int n = 0; n < N; ++n) acc += J.dz[(size_t)n * C + c] * J.h[(size_t)n * Hd + j];
+        } else {
+            for (int n = 0; n < N; ++n) acc += J.dz[(size_t)n * C + c] * act_fwd(J.h[(size_t)n * Hd + j], act);
+        }
         J.dW2[e] = acc;
         return;
     }
@@ -146,9 +152,9 @@ __global__ void __launch_bounds__(256) mlp_param_grad_kernel(MlpGradJobs jobs, i
     }
 }
 
-static int launch_mlp_param_grad(const MlpGradJobs& jobs, int njobs, int N, int C, int Hd, hipStream_t st) {
+static int launch_mlp_param_grad(const MlpGradJobs& jobs, int njobs, int N, int C, int Hd, int act, hipStream_t st) {
     const int total = 2 * Hd * C + Hd + C;
-    hipLaunchKernelGGL(mlp_param_grad_kernel, dim3(ceil_div(total, 256), njobs), dim3(256), 0, st, jobs, N, C, Hd);
+    hipLaunchKernelGGL(mlp_param_grad_kernel, dim3(ceil_div(total, 256), njobs), dim3(256), 0, st, jobs, N, C, Hd, act);
     DYNMM_LAUNCH_CHECK();
     return DYNMM_OK;
 }
@@ -158,7 +164,7 @@ __global__ void __launch_bounds__(256) se_coeff_bwd_kernel(
     const float* __restrict__ sd, SeParams P, const float* __restrict__ wc, int wc_stride,
     const float* __restrict__ hr, const float* __restrict__ hd, const float* __restrict__ gr,
     const float* __restrict__ gd, float* __restrict__ ws, float* __restrict__ dsr, float* __restrict__ dsd,
-    float* __restrict__ dwc, int dwc_stride, int N, int C, int use_se) {
+    float* __restrict__ dwc, int dwc_stride, int N, int C, int use_se, int act) {
     __shared__ float dg_lds[kMaxC];
     __shared__ float dz_lds[kMaxC];
     __shared__ float dh_lds[kMaxHid];
@@ -186,11 +192,11 @@ __global__ void __launch_bounds__(256) se_coeff_bwd_kernel(
     float* const dz_r = ws, * const dh_r = dz_r + (size_t)N * C;
     float* const dz_d = dh_r + (size_t)N * Hd, * const dh_d = dz_d + (size_t)N * C;
     se_mlp_bwd(dg_lds, hr + (size_t)n * Hd, gr + (size_t)n * C, P.p[0], P.p[2], dz_lds, dh_lds,
-               dz_r + (size_t)n * C, dh_r + (size_t)n * Hd, dsr + (size_t)n * C, C, Hd);
+               dz_r + (size_t)n * C, dh_r + (size_t)n * Hd, dsr + (size_t)n * C, C, Hd, act);
     for (int c = threadIdx.x; c < C; c += blockDim.x) dg_lds[c] = dbn[c] * (1.f - w);
     __syncthreads();
     se_mlp_bwd(dg_lds, hd + (size_t)n * Hd, gd + (size_t)n * C, P.p[4], P.p[6], dz_lds, dh_lds,
-               dz_d + (size_t)n * C, dh_d + (size_t)n * Hd, dsd + (size_t)n * C, C, Hd);
+               dz_d + (size_t)n * C, dh_d + (size_t)n * Hd, dsd + (size_t)n * C, C, Hd, act);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -395,7 +401,7 @@ __global__ void __launch_bounds__(256) reweigh_fwd_kernel(
     const float* __restrict__ wblend, int blend_mode, const float* __restrict__ prev, int prev_stride,
     const float* __restrict__ noise, unsigned long long seed, unsigned long long offset, float temp,
     int hard, float* __restrict__ a, float* __restrict__ b, float* __restrict__ wnext,
-    float* __restrict__ h, float* __restrict__ g, float* __restrict__ aux, int C) {
+    float* __restrict__ h, float* __restrict__ g, float* __restrict__ aux, int C, int act) {
     __shared__ float p_lds[kMaxC];
     __shared__ float h_lds[kMaxHid];
     __shared__ float red[4];
@@ -415,7 +421,7 @@ __global__ void __launch_bounds__(256) reweigh_fwd_kernel(
         p_lds[c] = c < C ? sr[(size_t)n * C + c] : sd[(size_t)n * C + (c - C)];
     __syncthreads();
     float* gn = g + (size_t)n * C2;
-    se_mlp_fwd(p_lds, P.p[0], P.p[1], P.p[2], P.p[3], h_lds, h + (size_t)n * Hd, gn, C2, Hd);
+    se_mlp_fwd(p_lds, P.p[0], P.p[1], P.p[2], P.p[3], h_lds, h + (size_t)n * Hd, gn, C2, Hd, act);
     float acc = 0.f;
     for (int c = threadIdx.x; c < C2; c += blockDim.x) acc += gn[c] * p_lds[c];   // same thread wrote gn[c]
     const float tot = block_reduce_sum_256<float>(acc, red);
@@ -455,7 +461,7 @@ __global__ void __launch_bounds__(256) reweigh_bwd_kernel(
     const float* __restrict__ sr, const float* __restrict__ sd, MlpParams P,
     const float* __restrict__ prev, int prev_stride, const float* __restrict__ h,
     const float* __restrict__ g, const float* __restrict__ aux, float* __restrict__ ws, float* __restrict__ dsr,
-    float* __restrict__ dsd, float* __restrict__ d_wblend, float* __restrict__ d_prev, float temp, int N, int C) {
+    float* __restrict__ dsd, float* __restrict__ d_wblend, float* __restrict__ d_prev, float temp, int N, int C, int act) {
     __shared__ float p_lds[kMaxC];
     __shared__ float dg_lds[kMaxC];
     __shared__ float dz_lds[kMaxC];
@@ -499,7 +505,7 @@ __global__ void __launch_bounds__(256) reweigh_bwd_kernel(
     const float* gn = g + (size_t)n * C2;
     float* const dz_g = ws, * const dh_g = ws + (size_t)N * C2;        // scratch: dz [N][2C] | dh [N][2C/16]
     se_mlp_bwd(dg_lds, h + (size_t)n * Hd, gn, P.p[0], P.p[2], dz_lds, dh_lds, dz_g + (size_t)n * C2,
-               dh_g + (size_t)n * Hd, ds_lds, C2, Hd);
+               dh_g + (size_t)n * Hd, ds_lds, C2, Hd, act);
     for (int c = threadIdx.x; c < C2; c += blockDim.x) {
         const float v = ds_lds[c] + dsn * gn[c];
         if (c < C) dsr[(size_t)n * C + c] = v;
@@ -511,12 +517,12 @@ __global__ void __launch_bounds__(256) reweigh_bwd_kernel(
 
 using namespace dynmm;
 
-extern "C" int dynmm_se_coeff_fwd(const float* sr, const float* sd, const float* const* params,
-                                  const float* wc, int wc_stride, float* a, float* b, float* hr,
-                                  float* hd, float* gr, float* gd, int N, int C, int use_se,
-                                  void* stream) {
+extern "C" int dynmm_se_coeff_fwd_act(const float* sr, const float* sd, const float* const* params,
+                                      const float* wc, int wc_stride, float* a, float* b, float* hr,
+                                      float* hd, float* gr, float* gd, int N, int C, int use_se, int act,
+                                      void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
-    if (!a || !b || N <= 0 || C <= 0 || C > kMaxC) return DYNMM_EINVAL;
+    if (!a || !b || N <= 0 || C <= 0 || C > kMaxC || !act_is_known(act)) return DYNMM_EINVAL;
     SeParams P{};
     if (use_se) {
         if (!sr || !sd || !params || !hr || !hd || !gr || !gd) return DYNMM_EINVAL;
@@ -527,22 +533,29 @@ extern "C" int dynmm_se_coeff_fwd(const float* sr, const float* sd, const float*
         }
     }
     hipLaunchKernelGGL(se_coeff_fwd_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, sr, sd, P, wc,
-                       wc_stride, a, b, hr, hd, gr, gd, C, use_se);
+                       wc_stride, a, b, hr, hd, gr, gd, C, use_se, act);
     DYNMM_LAUNCH_CHECK();
     return DYNMM_OK;
+}
+
+extern "C" int dynmm_se_coeff_fwd(const float* sr, const float* sd, const float* const* params,
+                                  const float* wc, int wc_stride, float* a, float* b, float* hr,
+                                  float* hd, float* gr, float* gd, int N, int C, int use_se,
+                                  void* stream) {
+    return dynmm_se_coeff_fwd_act(sr, sd, params, wc, wc_stride, a, b, hr, hd, gr, gd, N, C, use_se, DYNMM_ACT_RELU, stream);
 }
 
 extern "C" size_t dynmm_se_coeff_bwd_workspace_bytes(int N, int C) {
     return sizeof(float) * 2 * (size_t)N * (size_t)(C + C / 16);
 }
 
-extern "C" int dynmm_se_coeff_bwd(const float* da, const float* db, const float* sr, const float* sd,
-                                  const float* const* params, const float* wc, int wc_stride,
-                                  const float* hr, const float* hd, const float* gr, const float* gd,
-                                  float* const* dparams, float* dsr, float* dsd, float* dwc,
-                                  int dwc_stride, float* workspace, int N, int C, int use_se, void* stream) {
+extern "C" int dynmm_se_coeff_bwd_act(const float* da, const float* db, const float* sr, const float* sd,
+                                      const float* const* params, const float* wc, int wc_stride,
+                                      const float* hr, const float* hd, const float* gr, const float* gd,
+                                      float* const* dparams, float* dsr, float* dsd, float* dwc,
+                                      int dwc_stride, float* workspace, int N, int C, int use_se, int act, void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
-    if (!da || !db || N <= 0 || C <= 0 || C > kMaxC) return DYNMM_EINVAL;
+    if (!da || !db || N <= 0 || C <= 0 || C > kMaxC || !act_is_known(act)) return DYNMM_EINVAL;
     SeParams P{};
     hipStream_t st = (hipStream_t)stream;
     if (use_se) {
@@ -556,7 +569,7 @@ extern "C" int dynmm_se_coeff_bwd(const float* da, const float* db, const float*
         }
     }
     hipLaunchKernelGGL(se_coeff_bwd_kernel, dim3(N), dim3(256), 0, st, da, db, sr, sd, P, wc,
-                       wc_stride, hr, hd, gr, gd, workspace, dsr, dsd, dwc, dwc_stride, N, C, use_se);
+                       wc_stride, hr, hd, gr, gd, workspace, dsr, dsd, dwc, dwc_stride, N, C, use_se, act);
     DYNMM_LAUNCH_CHECK();
     if (use_se) {
         const int Hd = C / 16;
@@ -564,9 +577,18 @@ extern "C" int dynmm_se_coeff_bwd(const float* da, const float* db, const float*
         MlpGradJobs jobs{};
         jobs.j[0] = MlpGradJob{sr, hr, dz_r, dh_r, dparams[0], dparams[1], dparams[2], dparams[3], 0, nullptr};
         jobs.j[1] = MlpGradJob{sd, hd, dz_d, dh_d, dparams[4], dparams[5], dparams[6], dparams[7], 0, nullptr};
-        return launch_mlp_param_grad(jobs, 2, N, C, Hd, st);
+        return launch_mlp_param_grad(jobs, 2, N, C, Hd, act, st);
     }
     return DYNMM_OK;
+}
+
+extern "C" int dynmm_se_coeff_bwd(const float* da, const float* db, const float* sr, const float* sd,
+                                  const float* const* params, const float* wc, int wc_stride,
+                                  const float* hr, const float* hd, const float* gr, const float* gd,
+                                  float* const* dparams, float* dsr, float* dsd, float* dwc,
+                                  int dwc_stride, float* workspace, int N, int C, int use_se, void* stream) {
+    return dynmm_se_coeff_bwd_act(da, db, sr, sd, params, wc, wc_stride, hr, hd, gr, gd, dparams, dsr, dsd, dwc, dwc_stride,
+                                  workspace, N, C, use_se, DYNMM_ACT_RELU, stream);
 }
 
 extern "C" int dynmm_gate_head_fwd(const float* pooled, const float* fc, float* weight, float* wcum,
@@ -608,14 +630,14 @@ extern "C" int dynmm_gate_head_bwd(const float* d_weight, const float* d_wcum, c
     return DYNMM_OK;
 }
 
-extern "C" int dynmm_reweigh_fwd(const float* sr, const float* sd, const float* const* params,
-                                 const float* wblend, int blend_mode, const float* prev,
-                                 int prev_stride, const float* noise, unsigned long long seed,
-                                 unsigned long long offset, float temp, int hard, float* a, float* b,
-                                 float* wnext, float* h, float* g, float* aux, int N, int C,
-                                 void* stream) {
+extern "C" int dynmm_reweigh_fwd_act(const float* sr, const float* sd, const float* const* params,
+                                     const float* wblend, int blend_mode, const float* prev,
+                                     int prev_stride, const float* noise, unsigned long long seed,
+                                     unsigned long long offset, float temp, int hard, float* a, float* b,
+                                     float* wnext, float* h, float* g, float* aux, int N, int C, int act,
+                                     void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
-    if (N <= 0 || C <= 0 || (!a && !wnext) || (a && !b)) return DYNMM_EINVAL;
+    if (N <= 0 || C <= 0 || (!a && !wnext) || (a && !b) || !act_is_known(act)) return DYNMM_EINVAL;
     if (blend_mode < 0 || blend_mode > 2 || (a && blend_mode == 2 && !wblend)) return DYNMM_EINVAL;
     MlpParams P{};
     if (wnext) {
@@ -628,23 +650,33 @@ extern "C" int dynmm_reweigh_fwd(const float* sr, const float* sd, const float* 
     }
     hipLaunchKernelGGL(reweigh_fwd_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, sr, sd, P, wblend,
                        blend_mode, prev, prev_stride, noise, seed, offset, temp, hard, a, b, wnext, h, g,
-                       aux, C);
+                       aux, C, act);
     DYNMM_LAUNCH_CHECK();
     return DYNMM_OK;
+}
+
+extern "C" int dynmm_reweigh_fwd(const float* sr, const float* sd, const float* const* params,
+                                 const float* wblend, int blend_mode, const float* prev,
+                                 int prev_stride, const float* noise, unsigned long long seed,
+                                 unsigned long long offset, float temp, int hard, float* a, float* b,
+                                 float* wnext, float* h, float* g, float* aux, int N, int C,
+                                 void* stream) {
+    return dynmm_reweigh_fwd_act(sr, sd, params, wblend, blend_mode, prev, prev_stride, noise, seed, offset, temp, hard, a, b,
+                                 wnext, h, g, aux, N, C, DYNMM_ACT_RELU, stream);
 }
 
 extern "C" size_t dynmm_reweigh_bwd_workspace_bytes(int N, int C) {
     return sizeof(float) * (size_t)N * (size_t)(2 * C + (2 * C) / 16);
 }
 
-extern "C" int dynmm_reweigh_bwd(const float* d_wnext, const float* da, const float* db,
-                                 const float* sr, const float* sd, const float* const* params,
-                                 const float* prev, int prev_stride, const float* h, const float* g,
-                                 const float* aux, float* const* dparams, float* dsr, float* dsd,
-                                 float* d_wblend, float* d_prev, float* workspace, float temp, int N, int C,
-                                 void* stream) {
+extern "C" int dynmm_reweigh_bwd_act(const float* d_wnext, const float* da, const float* db,
+                                     const float* sr, const float* sd, const float* const* params,
+                                     const float* prev, int prev_stride, const float* h, const float* g,
+                                     const float* aux, float* const* dparams, float* dsr, float* dsd,
+                                     float* d_wblend, float* d_prev, float* workspace, float temp, int N, int C, int act,
+                                     void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
-    if (N <= 0 || C <= 0 || (!d_wnext && !d_wblend)) return DYNMM_EINVAL;
+    if (N <= 0 || C <= 0 || (!d_wnext && !d_wblend) || !act_is_known(act)) return DYNMM_EINVAL;
     if (d_wblend && (!da || !db)) return DYNMM_EINVAL;
     MlpParams P{};
     hipStream_t st = (hipStream_t)stream;
@@ -659,14 +691,24 @@ extern "C" int dynmm_reweigh_bwd(const float* d_wnext, const float* da, const fl
         }
     }
     hipLaunchKernelGGL(reweigh_bwd_kernel, dim3(N), dim3(256), 0, st, d_wnext, da, db, sr, sd, P, prev,
-                       prev_stride, h, g, aux, workspace, dsr, dsd, d_wblend, d_prev, temp, N, C);
+                       prev_stride, h, g, aux, workspace, dsr, dsd, d_wblend, d_prev, temp, N, C, act);
     DYNMM_LAUNCH_CHECK();
     if (d_wnext) {
         const int C2 = 2 * C, Hd = C2 / 16;
         MlpGradJobs jobs{};
         jobs.j[0] = MlpGradJob{sr, h, workspace, workspace + (size_t)N * C2, dparams[0], dparams[1], dparams[2],
                                dparams[3], C, sd};
-        return launch_mlp_param_grad(jobs, 1, N, C2, Hd, st);
+        return launch_mlp_param_grad(jobs, 1, N, C2, Hd, act, st);
     }
     return DYNMM_OK;
+}
+
+extern "C" int dynmm_reweigh_bwd(const float* d_wnext, const float* da, const float* db,
+                                 const float* sr, const float* sd, const float* const* params,
+                                 const float* prev, int prev_stride, const float* h, const float* g,
+                                 const float* aux, float* const* dparams, float* dsr, float* dsd,
+                                 float* d_wblend, float* d_prev, float* workspace, float temp, int N, int C,
+                                 void* stream) {
+    return dynmm_reweigh_bwd_act(d_wnext, da, db, sr, sd, params, prev, prev_stride, h, g, aux, dparams, dsr, dsd, d_wblend,
+                                 d_prev, workspace, temp, N, C, DYNMM_ACT_RELU, stream);
 }

@@ -52,6 +52,40 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const float* __restrict__
     }
 }
 
+// The same sums with every element widened to fp64 BEFORE it is squared.  bn_stats_kernel rounds x^2 to fp32, and the variance
+// is then E[x^2] - mu^2: with few values per channel whose spread is small against their mean (the 1x1 pyramid-pooling branch
+// normalises N values per channel; measured var / mu^2 down to 3e-4) the rounding of the squares is a relative error of 1e-4 ...
+// 1e-3 in var + eps, the saved invstd no longer belongs to the x it normalises, and the backward's cancelling combination
+// g - mean(g) - xhat mean(g xhat) carries that into the gradients (PPM at [2,512,3,4]: 1e-4 against 1e-5 with exact squares,
+// which is also what the CPU's batch norm shows).  Used by BatchNorm + Swish / Hswish; the ReLU path keeps
+// bn_stats_kernel and with it its results bit for bit.  HBM-bound like the other passes: the fp64 FMAs do not show.
+template <int V>
+__global__ void __launch_bounds__(256) bn_stats_f64_kernel(const float* __restrict__ x, double* __restrict__ sums,
+                                                           int N, int C, int HW) {
+    __shared__ double red[4];
+    const int c = blockIdx.x, S = gridDim.y;
+    double s1 = 0.0, s2 = 0.0;
+    for (int n = blockIdx.y; n < N; n += S) {
+        const float* p = x + ((size_t)n * C + c) * HW;
+        for (int i = threadIdx.x * V; i < HW; i += 256 * V) {
+            float v[V];
+            vload<V>(p + i, v);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const double d = (double)v[j];
+                s1 += d;
+                s2 = fma(d, d, s2);
+            }
+        }
+    }
+    const double t1 = block_reduce_sum_256<double>(s1, red);
+    const double t2 = block_reduce_sum_256<double>(s2, red);
+    if (threadIdx.x == 0) {
+        atomicAdd(&sums[c], t1);
+        atomicAdd(&sums[C + c], t2);
+    }
+}
+
 template <int V>
 __global__ void __launch_bounds__(256) bn_apply_kernel(
     const float* __restrict__ x, const double* __restrict__ sums, const float* __restrict__ gamma,
@@ -316,6 +350,138 @@ __global__ void __launch_bounds__(256) act_bwd_bias_kernel(
     }
 }
 
+// ---- the smooth activations (and any other code) THROUGH THE PRE-ACTIVATION ----------------------------------------------
+// a = act(z): one workgroup per 8192-element chunk of a plane, as bn_apply_kernel.
+template <int V>
+__global__ void __launch_bounds__(256) act_pre_fwd_kernel(const float* __restrict__ z, float* __restrict__ a, int HW, int act,
+                                                          int chunk) {
+    const size_t base = (size_t)blockIdx.x * HW;
+    const int beg = blockIdx.y * chunk;
+    const int end = min(HW, beg + chunk);
+    for (int i = beg + threadIdx.x * V; i < end; i += 256 * V) {
+        float v[V];
+        vload<V>(z + base + i, v);
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = act_fwd(v[j], act);
+        vstore<V>(a + base + i, v);
+    }
+}
+
+// dz = g * act'(z) ; dbias[split][c] = sum dz over the split's samples (act_bwd_bias_kernel's layout and fixed-order tail)
+template <int V>
+__global__ void __launch_bounds__(256) act_pre_bwd_kernel(
+    const float* __restrict__ g, const float* __restrict__ z, float* __restrict__ dz,
+    float* __restrict__ dbias, int N, int C, int HW, int act) {
+    __shared__ float red[4];
+    const int c = blockIdx.x, S = gridDim.y;
+    float s1 = 0.f;
+    for (int n = blockIdx.y; n < N; n += S) {
+        const size_t base = ((size_t)n * C + c) * HW;
+        float a1 = 0.f;
+        for (int i = threadIdx.x * V; i < HW; i += 256 * V) {
+            float gv[V], zv[V];
+            vload<V>(g + base + i, gv);
+            vload<V>(z + base + i, zv);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                gv[j] *= act_grad_pre(zv[j], act);
+                a1 += gv[j];
+            }
+            if (dz) vstore<V>(dz + base + i, gv);
+        }
+        s1 += a1;
+    }
+    if (dbias) {
+        const float t1 = block_reduce_sum_256<float>(s1, red);
+        if (threadIdx.x == 0) dbias[(size_t)blockIdx.y * C + c] = t1;
+    }
+}
+
+// bn_bwd_reduce_kernel with g_eff = g * act'(z), z re-evaluated from x (and the residual) by bn_apply_kernel's expression
+template <int V>
+__global__ void __launch_bounds__(256) bn_bwd_reduce_pre_kernel(
+    const float* __restrict__ g, const float* __restrict__ x, const float* __restrict__ residual,
+    const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
+    const float* __restrict__ beta, double* __restrict__ sums, int N, int C, int HW, int act) {
+    __shared__ float red[4];
+    const int c = blockIdx.x, S = gridDim.y;
+    const float mu = mean[c], is = invstd[c];
+    const float sc = gamma[c] * is;
+    const float sh = fmaf(-mu, sc, beta[c]);
+    float s1 = 0.f, s2 = 0.f;
+    for (int n = blockIdx.y; n < N; n += S) {
+        const size_t base = ((size_t)n * C + c) * HW;
+        float a1 = 0.f, a2 = 0.f;
+        for (int i = threadIdx.x * V; i < HW; i += 256 * V) {
+            float gv[V], xv[V], rv[V];
+            vload<V>(g + base + i, gv);
+            vload<V>(x + base + i, xv);
+            if (residual) vload<V>(residual + base + i, rv);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                float zz = fmaf(xv[j], sc, sh);
+                if (residual) zz += rv[j];
+                const float ge = gv[j] * act_grad_pre(zz, act);
+                a1 += ge;
+                a2 += ge * (xv[j] - mu) * is;
+            }
+        }
+        s1 += a1; s2 += a2;
+    }
+    const float t1 = block_reduce_sum_256<float>(s1, red);
+    const float t2 = block_reduce_sum_256<float>(s2, red);
+    if (threadIdx.x == 0) {
+        atomicAdd(&sums[c], (double)t1);
+        atomicAdd(&sums[C + c], (double)t2);
+    }
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) bn_bwd_apply_pre_kernel(
+    const float* __restrict__ g, const float* __restrict__ x, const float* __restrict__ residual,
+    const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const double* __restrict__ sums, float* __restrict__ dx,
+    float* __restrict__ dres, float* __restrict__ dgamma, float* __restrict__ dbeta, int N, int C, int HW,
+    int training, int act, int chunk) {
+    const int plane = blockIdx.x;
+    const int c = plane % C;
+    const float mu = mean[c], is = invstd[c];
+    const float k0 = gamma[c] * is;
+    const float sh = fmaf(-mu, k0, beta[c]);
+    double sg_d = sums[c], sgx_d = sums[C + c];
+    for (int s = 1; s < training; ++s) {
+        sg_d += sums[(size_t)(2 * s) * C + c];
+        sgx_d += sums[(size_t)(2 * s + 1) * C + c];
+    }
+    const float sg = (float)sg_d, sgx = (float)sgx_d;
+    if (plane < C && blockIdx.y == 0 && threadIdx.x == 0) {
+        if (dgamma) dgamma[c] = sgx;
+        if (dbeta) dbeta[c] = sg;
+    }
+    const float invM = 1.f / ((float)N * (float)HW);
+    const float m1 = training ? sg * invM : 0.f;
+    const float m2 = training ? sgx * invM : 0.f;
+    const size_t base = (size_t)plane * HW;
+    const int beg = blockIdx.y * chunk;
+    const int end = min(HW, beg + chunk);
+    for (int i = beg + threadIdx.x * V; i < end; i += 256 * V) {
+        float gv[V], xv[V], rv[V], o[V];
+        vload<V>(g + base + i, gv);
+        vload<V>(x + base + i, xv);
+        if (residual) vload<V>(residual + base + i, rv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float zz = fmaf(xv[j], k0, sh);
+            if (residual) zz += rv[j];
+            const float ge = gv[j] * act_grad_pre(zz, act);
+            gv[j] = ge;
+            o[j] = k0 * (ge - m1 - (xv[j] - mu) * is * m2);
+        }
+        vstore<V>(dx + base + i, o);
+        if (dres) vstore<V>(dres + base + i, gv);
+    }
+}
+
 static inline int plane_chunk(int HW, int* nchunks) {
     const int chunk = 8192;   // floats per workgroup pass: 8 x dwordx4 per lane
     *nchunks = (HW + chunk - 1) / chunk;
@@ -341,13 +507,27 @@ extern "C" int dynmm_bn_stats(const float* x, double* sums, int N, int C, int HW
     return DYNMM_OK;
 }
 
+extern "C" int dynmm_bn_stats_f64(const float* x, double* sums, int N, int C, int HW, int sums_are_zero, void* stream) {
+    (void)hipGetLastError();
+    if (!x || !sums || N <= 0 || C <= 0 || HW <= 0) return DYNMM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (!sums_are_zero) DYNMM_HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, st));
+    dim3 grid(C, reduce_splits(N, C));
+    if (can_vec4(HW, {x}))
+        hipLaunchKernelGGL(bn_stats_f64_kernel<4>, grid, dim3(256), 0, st, x, sums, N, C, HW);
+    else
+        hipLaunchKernelGGL(bn_stats_f64_kernel<1>, grid, dim3(256), 0, st, x, sums, N, C, HW);
+    DYNMM_LAUNCH_CHECK();
+    return DYNMM_OK;
+}
+
 extern "C" int dynmm_bn_apply(const float* x, const double* sums, const float* gamma,
                               const float* beta, float* running_mean, float* running_var,
                               float* save_mean, float* save_invstd, const float* residual, float* y,
                               long long* num_batches_tracked, int N, int C, int HW, float eps, float momentum,
                               int training, int act, unsigned long long* relu_bits, void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
-    if (!x || !gamma || !beta || !y || N <= 0 || C <= 0 || HW <= 0) return DYNMM_EINVAL;
+    if (!x || !gamma || !beta || !y || N <= 0 || C <= 0 || HW <= 0 || !act_is_known(act)) return DYNMM_EINVAL;
     if (relu_bits && (act != DYNMM_ACT_RELU || !can_vec4(HW, {x, residual, y}) || (reinterpret_cast<uintptr_t>(relu_bits) & 7u)))
         return DYNMM_EUNSUPPORTED;
     if (training && (!sums || (long long)N * HW <= 1)) return DYNMM_EINVAL;
@@ -394,6 +574,7 @@ extern "C" int dynmm_bn_bwd_reduce(const float* g, const float* y, const float* 
                                    const unsigned long long* relu_bits, void* stream) {
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
     if (!g || !x || !mean || !invstd || !sums || N <= 0 || C <= 0 || HW <= 0) return DYNMM_EINVAL;
+    if (act_is_smooth(act)) return DYNMM_EUNSUPPORTED;       // not a function of the output: dynmm_bn_bwd_reduce_pre
     if (act != DYNMM_ACT_NONE && !y && !relu_bits && (act != DYNMM_ACT_RELU || !gamma || !beta)) return DYNMM_EINVAL;
     if (relu_bits && (act != DYNMM_ACT_RELU || !can_vec4(HW, {g, x}) || (reinterpret_cast<uintptr_t>(relu_bits) & 7u)))
         return DYNMM_EUNSUPPORTED;
@@ -419,6 +600,7 @@ extern "C" int dynmm_bn_bwd_apply(const float* g, const float* y, const float* x
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
     if (!g || !x || !mean || !invstd || !gamma || !sums || !dx || N <= 0 || C <= 0 || HW <= 0)
         return DYNMM_EINVAL;
+    if (act_is_smooth(act)) return DYNMM_EUNSUPPORTED;       // not a function of the output: dynmm_bn_bwd_apply_pre
     if (act != DYNMM_ACT_NONE && !y && !relu_bits && (act != DYNMM_ACT_RELU || !beta || d_residual)) return DYNMM_EINVAL;
     if (relu_bits && (act != DYNMM_ACT_RELU || !can_vec4(HW, {g, x, dx, d_residual}) || (reinterpret_cast<uintptr_t>(relu_bits) & 7u)))
         return DYNMM_EUNSUPPORTED;
@@ -461,6 +643,7 @@ extern "C" int dynmm_act_bwd_bias(const float* g, const float* y, float* g_out, 
     (void)hipGetLastError();   // drop stale errors left by other users of the runtime
     if (!g || N <= 0 || C <= 0 || HW <= 0) return DYNMM_EINVAL;
     if (act != DYNMM_ACT_NONE && !y) return DYNMM_EINVAL;
+    if (act_is_smooth(act)) return DYNMM_EUNSUPPORTED;       // not a function of the output: dynmm_act_pre_bwd
     if (!g_out && !dbias) return DYNMM_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int S = reduce_splits(N, C);
@@ -476,5 +659,83 @@ extern "C" int dynmm_act_bwd_bias(const float* g, const float* y, float* g_out, 
         launch_reduce_slabs(part, dbias, C, S, st);
         DYNMM_LAUNCH_CHECK();
     }
+    return DYNMM_OK;
+}
+
+extern "C" int dynmm_act_pre_fwd(const float* z, float* a, int N, int C, int HW, int act, void* stream) {
+    (void)hipGetLastError();
+    if (!z || !a || N <= 0 || C <= 0 || HW <= 0 || !act_is_known(act)) return DYNMM_EINVAL;
+    int nchunks;
+    const int chunk = plane_chunk(HW, &nchunks);
+    dim3 grid(N * C, nchunks);
+    hipStream_t st = (hipStream_t)stream;
+    if (can_vec4(HW, {z, a}))
+        hipLaunchKernelGGL(act_pre_fwd_kernel<4>, grid, dim3(256), 0, st, z, a, HW, act, chunk);
+    else
+        hipLaunchKernelGGL(act_pre_fwd_kernel<1>, grid, dim3(256), 0, st, z, a, HW, act, chunk);
+    DYNMM_LAUNCH_CHECK();
+    return DYNMM_OK;
+}
+
+extern "C" int dynmm_act_pre_bwd(const float* g, const float* z, float* dz, float* dbias, float* workspace,
+                                 int N, int C, int HW, int act, void* stream) {
+    (void)hipGetLastError();
+    if (!g || !z || N <= 0 || C <= 0 || HW <= 0 || !act_is_known(act)) return DYNMM_EINVAL;
+    if (!dz && !dbias) return DYNMM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int S = reduce_splits(N, C);
+    if (dbias && S > 1 && !workspace) return DYNMM_EWORKSPACE;
+    float* part = (dbias && S > 1) ? workspace : dbias;
+    dim3 grid(C, S);
+    if (can_vec4(HW, {g, z, dz}))
+        hipLaunchKernelGGL(act_pre_bwd_kernel<4>, grid, dim3(256), 0, st, g, z, dz, part, N, C, HW, act);
+    else
+        hipLaunchKernelGGL(act_pre_bwd_kernel<1>, grid, dim3(256), 0, st, g, z, dz, part, N, C, HW, act);
+    DYNMM_LAUNCH_CHECK();
+    if (dbias && S > 1) {
+        launch_reduce_slabs(part, dbias, C, S, st);
+        DYNMM_LAUNCH_CHECK();
+    }
+    return DYNMM_OK;
+}
+
+extern "C" int dynmm_bn_bwd_reduce_pre(const float* g, const float* x, const float* residual, const float* mean,
+                                       const float* invstd, const float* gamma, const float* beta, double* sums, int N, int C,
+                                       int HW, int act, int sums_are_zero, void* stream) {
+    (void)hipGetLastError();
+    if (!g || !x || !mean || !invstd || !gamma || !beta || !sums || N <= 0 || C <= 0 || HW <= 0 || !act_is_known(act))
+        return DYNMM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (!sums_are_zero) DYNMM_HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, st));
+    dim3 grid(C, reduce_splits(N, C));
+    if (can_vec4(HW, {g, x, residual}))
+        hipLaunchKernelGGL(bn_bwd_reduce_pre_kernel<4>, grid, dim3(256), 0, st, g, x, residual, mean, invstd, gamma, beta,
+                           sums, N, C, HW, act);
+    else
+        hipLaunchKernelGGL(bn_bwd_reduce_pre_kernel<1>, grid, dim3(256), 0, st, g, x, residual, mean, invstd, gamma, beta,
+                           sums, N, C, HW, act);
+    DYNMM_LAUNCH_CHECK();
+    return DYNMM_OK;
+}
+
+extern "C" int dynmm_bn_bwd_apply_pre(const float* g, const float* x, const float* residual, const float* mean,
+                                      const float* invstd, const float* gamma, const float* beta, const double* sums,
+                                      float* dx, float* d_residual, float* dgamma, float* dbeta, int N, int C, int HW,
+                                      int training, int act, void* stream) {
+    (void)hipGetLastError();
+    if (!g || !x || !mean || !invstd || !gamma || !beta || !sums || !dx || N <= 0 || C <= 0 || HW <= 0 || training < 0 ||
+        !act_is_known(act))
+        return DYNMM_EINVAL;
+    int nchunks;
+    const int chunk = plane_chunk(HW, &nchunks);
+    dim3 grid(N * C, nchunks);
+    hipStream_t st = (hipStream_t)stream;
+    if (can_vec4(HW, {g, x, residual, dx, d_residual}))
+        hipLaunchKernelGGL(bn_bwd_apply_pre_kernel<4>, grid, dim3(256), 0, st, g, x, residual, mean, invstd, gamma, beta,
+                           sums, dx, d_residual, dgamma, dbeta, N, C, HW, training, act, chunk);
+    else
+        hipLaunchKernelGGL(bn_bwd_apply_pre_kernel<1>, grid, dim3(256), 0, st, g, x, residual, mean, invstd, gamma, beta,
+                           sums, dx, d_residual, dgamma, dbeta, N, C, HW, training, act, chunk);
+    DYNMM_LAUNCH_CHECK();
     return DYNMM_OK;
 }

@@ -11,9 +11,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libdynmm_hip.so')
 CSRC = os.path.join(_HERE, 'csrc')
 
-ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_TANH, ACT_SWISH, ACT_HSWISH = 0, 1, 2, 3, 4
+SMOOTH_ACTS = (ACT_SWISH, ACT_HSWISH)      # not invertible: their backward needs the pre-activation (csrc/common.h)
 DYNMM_OK, DYNMM_EINVAL, DYNMM_EUNSUPPORTED, DYNMM_EWORKSPACE = 0, -1, -2, -3
-ACT = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2}
+ACT = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'swish': 3, 'silu': 3, 'hswish': 4}
 LOSS_BCE_LOGITS, LOSS_L1 = 0, 1          # dynmm_head_loss kinds
 
 c_f = C.c_void_p       # device pointers travel as void* (tensor.data_ptr() or None)
@@ -88,11 +89,16 @@ SIGNATURES = {
     'dynmm_conv2d_wgrad_group': (c_i, [c_i, c_f, c_f, c_f, c_f, c_f, c_sz, _GP, c_f]),
     'dynmm_act_bwd_bias_workspace_bytes': (c_sz, [c_i, c_i]),
     'dynmm_act_bwd_bias': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    'dynmm_act_pre_fwd': (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    'dynmm_act_pre_bwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     'dynmm_bn_stats': (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    'dynmm_bn_stats_f64': (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     'dynmm_bn_relu_bits_words': (c_sz, [c_i, c_i, c_i]),
     'dynmm_bn_apply': (c_i, [c_f] * 11 + [c_i, c_i, c_i, c_fl, c_fl, c_i, c_i, c_f, c_f]),
     'dynmm_bn_bwd_reduce': (c_i, [c_f] * 8 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     'dynmm_bn_bwd_apply': (c_i, [c_f] * 12 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    'dynmm_bn_bwd_reduce_pre': (c_i, [c_f] * 8 + [c_i, c_i, c_i, c_i, c_i, c_f]),
+    'dynmm_bn_bwd_apply_pre': (c_i, [c_f] * 12 + [c_i, c_i, c_i, c_i, c_i, c_f]),
     'dynmm_bn_fold': (c_i, [c_f] * 7 + [c_i, c_fl, c_f]),
     'dynmm_maxpool3x3s2_fwd': (c_i, [c_f, c_f, c_f] + [c_i] * 6 + [c_f]),
     'dynmm_maxpool3x3s2_bwd': (c_i, [c_f, c_f, c_f] + [c_i] * 6 + [c_f]),
@@ -111,6 +117,8 @@ SIGNATURES = {
     'dynmm_bilinear_into_bwd': (c_i, [c_f, c_f] + [c_i] * 8 + [c_f]),
     'dynmm_gap2_fwd': (c_i, [c_f] * 4 + [c_i, c_i, c_f]),
     'dynmm_se_coeff_fwd': (c_i, [c_f, c_f, _PP, c_f, c_i] + [c_f] * 6 + [c_i, c_i, c_i, c_f]),
+    'dynmm_se_coeff_fwd_act': (c_i, [c_f, c_f, _PP, c_f, c_i] + [c_f] * 6 + [c_i, c_i, c_i, c_i, c_f]),
+    'dynmm_se_coeff_bwd_act': (c_i, [c_f] * 4 + [_PP, c_f, c_i] + [c_f] * 4 + [_PP, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     'dynmm_se_coeff_bwd_workspace_bytes': (c_sz, [c_i, c_i]),
     'dynmm_se_coeff_bwd': (c_i, [c_f] * 4 + [_PP, c_f, c_i] + [c_f] * 4 + [_PP, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_f]),
     'dynmm_axpby_fwd': (c_i, [c_f] * 5 + [c_i, c_i, c_f]),
@@ -126,6 +134,10 @@ SIGNATURES = {
     'dynmm_axpby_pool_bwd_apply': (c_i, [c_f] * 8 + [C.c_float] + [c_f] * 2 + [c_i] * 3 + [c_f]),
     'dynmm_reweigh_fwd': (c_i, [c_f, c_f, _PP, c_f, c_i, c_f, c_i, c_f, C.c_ulonglong, C.c_ulonglong, c_fl, c_i]
                           + [c_f] * 6 + [c_i, c_i, c_f]),
+    'dynmm_reweigh_fwd_act': (c_i, [c_f, c_f, _PP, c_f, c_i, c_f, c_i, c_f, C.c_ulonglong, C.c_ulonglong, c_fl, c_i]
+                              + [c_f] * 6 + [c_i, c_i, c_i, c_f]),
+    'dynmm_reweigh_bwd_act': (c_i, [c_f] * 5 + [_PP, c_f, c_i, c_f, c_f, c_f, _PP, c_f, c_f, c_f, c_f, c_f, c_fl, c_i, c_i, c_i,
+                                    c_f]),
     'dynmm_reweigh_bwd_workspace_bytes': (c_sz, [c_i, c_i]),
     'dynmm_reweigh_bwd': (c_i, [c_f] * 5 + [_PP, c_f, c_i, c_f, c_f, c_f, _PP, c_f, c_f, c_f, c_f, c_f, c_fl, c_i, c_i, c_f]),
     'dynmm_gate_head_fwd': (c_i, [c_f] * 8 + [c_i, c_i, c_fl, c_i, c_i, c_f]),

@@ -8,6 +8,17 @@ import torch.nn as nn
 
 from .. import ops
 
+ACTIVATIONS = {'relu': 'relu', 'swish': 'swish', 'silu': 'swish', 'hswish': 'hswish'}
+
+
+def normalize_activation(activation):
+    """The reference's spellings (model.py:46-56: case-insensitive relu | swish | silu | hswish) -> 'relu' | 'swish' | 'hswish'."""
+    key = activation.lower() if isinstance(activation, str) else activation
+    if key not in ACTIVATIONS:
+        raise NotImplementedError('Only relu, swish and hswish as activation function are supported so far. '
+                                  'Got {}'.format(activation))
+    return ACTIVATIONS[key]
+
 
 def conv_bn_act(x, conv, bn, act=None, residual=None, x2=None, mask_input=False, conv_link=None, res_link=None, bwd_link=None):
     """act(BN(conv(x|x2)) + residual).
@@ -24,24 +35,26 @@ def conv_bn_act(x, conv, bn, act=None, residual=None, x2=None, mask_input=False,
 
 
 class ConvBNAct(nn.Sequential):
-    """conv (no bias) -> BN -> ReLU; keys '<p>.conv.weight', '<p>.bn.*' (model_utils.py:11-23)."""
+    """conv (no bias) -> BN -> activation; keys '<p>.conv.weight', '<p>.bn.*' (model_utils.py:11-23)."""
 
-    def __init__(self, cin, cout, kernel_size):
+    def __init__(self, cin, cout, kernel_size, activation='relu'):
         super().__init__()
+        self.activation = normalize_activation(activation)
         self.add_module('conv', nn.Conv2d(cin, cout, kernel_size, padding=kernel_size // 2, bias=False))
         self.add_module('bn', nn.BatchNorm2d(cout))
 
     def forward(self, x):
-        return conv_bn_act(x, self.conv, self.bn, 'relu')
+        return conv_bn_act(x, self.conv, self.bn, self.activation)
 
 
 class NonBottleneck1D(nn.Module):
     """ERFNet factorised residual block (resnet.py:87-147): 3x1 -> ReLU -> 1x3 -> BN(eps 1e-3) ->
-    ReLU -> 3x1 -> ReLU -> 1x3 -> BN -> (+identity) -> ReLU; stride is split (s,1)/(1,s)."""
+    ReLU -> 3x1 -> ReLU -> 1x3 -> BN -> (+identity) -> ReLU; stride is split (s,1)/(1,s).  `activation` replaces all four."""
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, activation='relu'):
         super().__init__()
+        self.activation = normalize_activation(activation)
         self.conv3x1_1 = nn.Conv2d(inplanes, planes, (3, 1), stride=(stride, 1), padding=(1, 0))
         self.conv1x3_1 = nn.Conv2d(planes, planes, (1, 3), stride=(1, stride), padding=(0, 1))
         self.bn1 = nn.BatchNorm2d(planes, eps=1e-3)
@@ -56,22 +69,26 @@ class NonBottleneck1D(nn.Module):
         # Backward fusions (forward results unchanged): the ReLU backward of each 3x1 conv is applied in
         # the dgrad epilogue of the 1x3 conv that consumes it, and the identity branch's gradient is
         # added in the dgrad epilogue of the first conv instead of a separate autograd add pass.
-        fuse_bwd = torch.is_grad_enabled() and x.requires_grad
-        link = ops.GradLink() if (fuse_bwd and self.downsample is None) else None
-        in_link = getattr(x, '_bn_out_link', None) if (chain and link is not None) else None
+        act = self.activation
+        grad = torch.is_grad_enabled() and x.requires_grad
+        # (Swish / Hswish have no decisions to defer: the mask / BNLink hints are not constructed at all; the identity branch's
+        #  gradient still rides in the first convolution's input-gradient epilogue — GradLink is activation-independent)
+        fuse_bwd = grad and act == 'relu'
+        link = ops.GradLink() if (grad and self.downsample is None) else None
+        in_link = getattr(x, '_bn_out_link', None) if (chain and link is not None and fuse_bwd) else None
         xd = x
         if self.downsample is not None:
             x, xd = ops.fan_out(x, 2)            # x feeds the first conv AND the down-sample conv: one fused gradient sum
         c = self.conv3x1_1
-        y = ops.conv2d(x, c.weight, c.bias, c.stride, c.padding, 'relu', defer_mask=fuse_bwd, link=link, bn_link=in_link)
+        y = ops.conv2d(x, c.weight, c.bias, c.stride, c.padding, act, defer_mask=fuse_bwd, link=link, bn_link=in_link)
         # bn1 + ReLU feed conv3x1_2 and nothing else: its input-gradient launch also does bn1's backward reductions (ops.BNLink)
         bnl = ops.BNLink() if (fuse_bwd and self.bn1.training) else None
-        y = conv_bn_act(y, self.conv1x3_1, self.bn1, 'relu', mask_input=fuse_bwd, bwd_link=bnl)
+        y = conv_bn_act(y, self.conv1x3_1, self.bn1, act, mask_input=fuse_bwd, bwd_link=bnl)
         c = self.conv3x1_2
-        y = ops.conv2d(y, c.weight, c.bias, c.stride, c.padding, 'relu', defer_mask=fuse_bwd, bn_link=bnl)
+        y = ops.conv2d(y, c.weight, c.bias, c.stride, c.padding, act, defer_mask=fuse_bwd, bn_link=bnl)
         idt = x if self.downsample is None else conv_bn_act(xd, self.downsample[0], self.downsample[1])
         out_link = ops.BNLink() if (fuse_bwd and self.bn2.training) else None
-        out = conv_bn_act(y, self.conv1x3_2, self.bn2, 'relu', residual=idt, mask_input=fuse_bwd, res_link=link, bwd_link=out_link)
+        out = conv_bn_act(y, self.conv1x3_2, self.bn2, act, residual=idt, mask_input=fuse_bwd, res_link=link, bwd_link=out_link)
         if out_link is not None and out_link.bits is not None:
             out._bn_out_link = out_link            # picked up by the next block of the stage (chain=True), by nothing else
         return out
@@ -81,8 +98,9 @@ class BasicBlock(nn.Module):
     """Two 3x3 conv + BN, residual, ReLU (resnet.py:42-84)."""
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, activation='relu'):
         super().__init__()
+        self.activation = normalize_activation(activation)
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride=stride, padding=1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
         self.conv2 = nn.Conv2d(planes, planes, 3, padding=1, bias=False)
@@ -95,9 +113,9 @@ class BasicBlock(nn.Module):
         xd = x
         if self.downsample is not None:
             x, xd = ops.fan_out(x, 2)
-        y = conv_bn_act(x, self.conv1, self.bn1, 'relu', conv_link=link)
+        y = conv_bn_act(x, self.conv1, self.bn1, self.activation, conv_link=link)
         idt = x if self.downsample is None else conv_bn_act(xd, self.downsample[0], self.downsample[1])
-        return conv_bn_act(y, self.conv2, self.bn2, 'relu', residual=idt, res_link=link)
+        return conv_bn_act(y, self.conv2, self.bn2, self.activation, residual=idt, res_link=link)
 
 
 class Bottleneck(nn.Module):
@@ -105,8 +123,9 @@ class Bottleneck(nn.Module):
     block (resnet.py:150-192); `--encoder resnet50` is the reference CLI's default (src/args.py:105)."""
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, activation='relu'):
         super().__init__()
+        self.activation = normalize_activation(activation)
         self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
         self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
@@ -121,10 +140,10 @@ class Bottleneck(nn.Module):
         xd = x
         if self.downsample is not None:
             x, xd = ops.fan_out(x, 2)
-        y = conv_bn_act(x, self.conv1, self.bn1, 'relu', conv_link=link)
-        y = conv_bn_act(y, self.conv2, self.bn2, 'relu')
+        y = conv_bn_act(x, self.conv1, self.bn1, self.activation, conv_link=link)
+        y = conv_bn_act(y, self.conv2, self.bn2, self.activation)
         idt = x if self.downsample is None else conv_bn_act(xd, self.downsample[0], self.downsample[1])
-        return conv_bn_act(y, self.conv3, self.bn3, 'relu', residual=idt, res_link=link)
+        return conv_bn_act(y, self.conv3, self.bn3, self.activation, residual=idt, res_link=link)
 
 
 def chain_ok(prev, blk):
@@ -145,8 +164,9 @@ LAYERS = {'resnet18': (2, 2, 2, 2), 'resnet34': (3, 4, 6, 3), 'resnet50': (3, 4,
 class ResNetEncoder(nn.Module):
     """ResNet-18/34 trunk with stage-wise entry points (resnet.py:195-379)."""
 
-    def __init__(self, name, block, input_channels=3):
+    def __init__(self, name, block, input_channels=3, activation='relu'):
         super().__init__()
+        self.activation = normalize_activation(activation)
         if name not in LAYERS:
             raise NotImplementedError(f'Only {sorted(LAYERS)} encoders are implemented on the HIP path. Got {name}')
         if block not in BLOCKS and name != 'resnet50':
@@ -164,7 +184,8 @@ class ResNetEncoder(nn.Module):
             if stride != 1 or inplanes != planes * ex:
                 down = nn.Sequential(nn.Conv2d(inplanes, planes * ex, 1, stride=stride, bias=False),
                                      nn.BatchNorm2d(planes * ex))
-            stage = [blk(inplanes, planes, stride, down)] + [blk(planes * ex, planes) for _ in range(n - 1)]
+            stage = [blk(inplanes, planes, stride, down, activation=self.activation)] + \
+                [blk(planes * ex, planes, activation=self.activation) for _ in range(n - 1)]
             setattr(self, f'layer{j}', nn.Sequential(*stage))
             inplanes = planes * ex
         self.down_2_channels_out = 64
@@ -178,7 +199,7 @@ class ResNetEncoder(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def forward_first_conv(self, x):
-        return conv_bn_act(x, self.conv1, self.bn1, 'relu')
+        return conv_bn_act(x, self.conv1, self.bn1, self.activation)
 
     def _stage(self, x, j):
         """The blocks of stage j in sequence.  THE CHAIN CONTRACT (ops.BNLink, BNRED = 2): `chain=True` tells block i that the

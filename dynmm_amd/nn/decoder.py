@@ -43,12 +43,12 @@ class Upsample(nn.Module):
 
 class DecoderModule(nn.Module):
     def __init__(self, channels_in, channels_dec, nr_decoder_blocks, num_classes, upsampling_mode='learned-3x3-zeropad',
-                 encoder_decoder_fusion='add'):
+                 encoder_decoder_fusion='add', activation='relu'):
         super().__init__()
         self.upsampling_mode = upsampling_mode
         self.encoder_decoder_fusion = encoder_decoder_fusion
-        self.conv3x3 = ConvBNAct(channels_in, channels_dec, 3)
-        self.decoder_blocks = nn.Sequential(*[NonBottleneck1D(channels_dec, channels_dec)
+        self.conv3x3 = ConvBNAct(channels_in, channels_dec, 3, activation)
+        self.decoder_blocks = nn.Sequential(*[NonBottleneck1D(channels_dec, channels_dec, activation=activation)
                                               for _ in range(nr_decoder_blocks)])
         self.upsample = Upsample(upsampling_mode, channels_dec)
         self.side_output = nn.Conv2d(channels_dec, num_classes, 1)
@@ -70,10 +70,10 @@ class DecoderModule(nn.Module):
 
 class Decoder(nn.Module):
     def __init__(self, channels_in, channels_decoder, nr_decoder_blocks, num_classes,
-                 upsampling_mode='learned-3x3-zeropad', encoder_decoder_fusion='add'):
+                 upsampling_mode='learned-3x3-zeropad', encoder_decoder_fusion='add', activation='relu'):
         super().__init__()
         cd = channels_decoder
-        kw = dict(upsampling_mode=upsampling_mode, encoder_decoder_fusion=encoder_decoder_fusion)
+        kw = dict(upsampling_mode=upsampling_mode, encoder_decoder_fusion=encoder_decoder_fusion, activation=activation)
         self.decoder_module_1 = DecoderModule(channels_in, cd[0], nr_decoder_blocks[0], num_classes, **kw)
         self.decoder_module_2 = DecoderModule(cd[0], cd[1], nr_decoder_blocks[1], num_classes, **kw)
         self.decoder_module_3 = DecoderModule(cd[1], cd[2], nr_decoder_blocks[2], num_classes, **kw)

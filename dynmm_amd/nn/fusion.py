@@ -2,11 +2,14 @@
 excitation MLPs, channel scaling, modality sum AND the gate blend) runs in ops.se_fuse_blend."""
 import torch.nn as nn
 
+from .blocks import normalize_activation
+
 
 class SqueezeAndExcitation(nn.Module):
-    def __init__(self, channel, reduction=16):
+    def __init__(self, channel, reduction=16, activation='relu'):
         super().__init__()
-        # indices 1 and 3 are the (parameter-free) ReLU / Sigmoid slots of the reference Sequential
+        self.activation = normalize_activation(activation)          # the hidden layer's (ops.se_fuse_blend se_act)
+        # indices 1 and 3 are the (parameter-free) activation / Sigmoid slots of the reference Sequential
         self.fc = nn.Sequential(nn.Conv2d(channel, channel // reduction, 1), nn.Identity(),
                                 nn.Conv2d(channel // reduction, channel, 1), nn.Identity())
 
@@ -15,10 +18,11 @@ class SqueezeAndExcitation(nn.Module):
 
 
 class SqueezeAndExciteFusionAdd(nn.Module):
-    def __init__(self, channels_in):
+    def __init__(self, channels_in, activation='relu'):
         super().__init__()
-        self.se_rgb = SqueezeAndExcitation(channels_in)
-        self.se_depth = SqueezeAndExcitation(channels_in)
+        self.activation = activation = normalize_activation(activation)
+        self.se_rgb = SqueezeAndExcitation(channels_in, activation=activation)
+        self.se_depth = SqueezeAndExcitation(channels_in, activation=activation)
 
     def params8(self):
         return self.se_rgb.mlp_params() + self.se_depth.mlp_params()
@@ -28,8 +32,9 @@ class SqueezeAndExcitationWeight(nn.Module):
     """Parameter container of model_utils.py:54-70 (the `linear` layer is unused by the reference's
     forward but part of its state_dict)."""
 
-    def __init__(self, channel, reduction=16):
+    def __init__(self, channel, reduction=16, activation='relu'):
         super().__init__()
+        self.activation = activation = normalize_activation(activation)
         self.fc = nn.Sequential(nn.Conv2d(channel, channel // reduction, 1), nn.Identity(),
                                 nn.Conv2d(channel // reduction, channel, 1), nn.Identity())
         self.linear = nn.Linear(channel, 2)
@@ -42,10 +47,11 @@ class SqueezeAndExciteReweigh(nn.Module):
     """Per-stage 2-way Gumbel gate (rgb_depth_fusion.py:29-65).  Stand-alone call evaluates the gate only;
     inside SkipESANet the gate is fused with the stage blend (ops.reweigh_fuse)."""
 
-    def __init__(self, temp, channels_in):
+    def __init__(self, temp, channels_in, activation='relu'):
         super().__init__()
         self.temp = temp
-        self.se = SqueezeAndExcitationWeight(channels_in * 2)
+        self.activation = activation = normalize_activation(activation)
+        self.se = SqueezeAndExcitationWeight(channels_in * 2, activation=activation)
         self.act = nn.Identity()          # nn.Sigmoid() slot: parameter-free
 
     def random_weights(self, bs, device, prev_weight=None):
@@ -62,5 +68,5 @@ class SqueezeAndExciteReweigh(nn.Module):
         if random:
             return self.random_weights(rgb.shape[0], rgb.device, prev_weight).view(-1, 2, 1, 1)
         _, w, _ = ops.reweigh_fuse(rgb, depth, None, 0, self.se.mlp_params(), self.temp, hard or test,
-                                   prev_weight, noise)
+                                   prev_weight, noise, se_act=self.activation)
         return w.view(-1, 2, 1, 1)

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .blocks import ConvBNAct, ResNetEncoder, conv_bn_act
+from .blocks import ConvBNAct, ResNetEncoder, conv_bn_act, normalize_activation
 from .context import get_context_module
 from .decoder import UPSAMPLING_MODES, Decoder
 from .fusion import SqueezeAndExciteFusionAdd
@@ -90,7 +90,7 @@ def check_decoder_options(upsampling, encoder_decoder_fusion):
 
 
 def build_decoder_side(model, channels_decoder, nr_decoder_blocks, num_classes, context_module, upsampling,
-                       encoder_decoder_fusion):
+                       encoder_decoder_fusion, activation='relu'):
     """Skip layers, context module and decoder of the three networks (…globalgate.py:145-207, model_skip_mod.py:139-199,
     model.py:127-187).  encoder_decoder_fusion 'add': skip_layer1..3 = ConvBNAct 1x1 where the channel counts differ,
     else an empty Sequential; 'None': skip_layer0..3 = nn.Identity and the decoder adds nothing.  The context module
@@ -101,16 +101,16 @@ def build_decoder_side(model, channels_decoder, nr_decoder_blocks, num_classes, 
         for j, (cin, cout) in enumerate(((enc.down_4_channels_out, channels_decoder[2]),
                                          (enc.down_8_channels_out, channels_decoder[1]),
                                          (enc.down_16_channels_out, channels_decoder[0])), start=1):
-            setattr(model, f'skip_layer{j}', nn.Sequential(*([ConvBNAct(cin, cout, 1)] if cin != cout else [])))
+            setattr(model, f'skip_layer{j}', nn.Sequential(*([ConvBNAct(cin, cout, 1, activation)] if cin != cout else [])))
     else:
         for j in range(4):
             setattr(model, f'skip_layer{j}', nn.Identity())
     ctx_mode = 'nearest' if 'learned-3x3' in upsampling else upsampling
     model.context_module, ch_ctx = get_context_module(context_module, enc.down_32_channels_out, channels_decoder[0],
                                                       input_size=(model.height // 32, model.width // 32),
-                                                      upsampling_mode=ctx_mode)
+                                                      activation=activation, upsampling_mode=ctx_mode)
     model.decoder = Decoder(ch_ctx, channels_decoder, nr_decoder_blocks, num_classes, upsampling_mode=upsampling,
-                            encoder_decoder_fusion=encoder_decoder_fusion)
+                            encoder_decoder_fusion=encoder_decoder_fusion, activation=activation)
 
 
 def decoder_skip(model, j, fuse):
@@ -139,9 +139,7 @@ class SkipGateESANet(nn.Module):
         super().__init__()
         channels_decoder = [128, 128, 128] if channels_decoder is None else list(channels_decoder)
         nr_decoder_blocks = [3, 3, 3] if nr_decoder_blocks is None else list(nr_decoder_blocks)
-        if activation.lower() != 'relu':
-            raise NotImplementedError('Only relu is implemented as activation on the HIP path. '
-                                      'Got {}'.format(activation))
+        self.activation = activation = normalize_activation(activation)      # 'relu' | 'swish' | 'hswish' (model...py:64-74)
         check_decoder_options(upsampling, encoder_decoder_fusion)
         if fuse_depth_in_rgb_encoder not in ('add', 'SE-add'):
             raise NotImplementedError('fuse_depth_in_rgb_encoder must be "add" or "SE-add"')
@@ -149,8 +147,8 @@ class SkipGateESANet(nn.Module):
         self.block_rule = block_rule if block_rule else [1, 1, 1, 1]
         self.height, self.width = height, width
 
-        self.encoder_rgb = ResNetEncoder(encoder_rgb, encoder_block, input_channels=3)
-        self.encoder_depth = ResNetEncoder(encoder_depth, encoder_block, input_channels=1)
+        self.encoder_rgb = ResNetEncoder(encoder_rgb, encoder_block, input_channels=3, activation=activation)
+        self.encoder_depth = ResNetEncoder(encoder_depth, encoder_block, input_channels=1, activation=activation)
         if pretrained_on_imagenet:
             # resnet.py:395-509, from local files (raises FileNotFoundError when they are absent — never a silent
             # random initialisation)
@@ -163,10 +161,10 @@ class SkipGateESANet(nn.Module):
         if fuse_depth_in_rgb_encoder == 'SE-add':
             for j, ch in enumerate((64, enc.down_4_channels_out, enc.down_8_channels_out,
                                     enc.down_16_channels_out, enc.down_32_channels_out)):
-                setattr(self, f'se_layer{j}', SqueezeAndExciteFusionAdd(ch))
+                setattr(self, f'se_layer{j}', SqueezeAndExciteFusionAdd(ch, activation=activation))
 
         build_decoder_side(self, channels_decoder, nr_decoder_blocks, num_classes, context_module, upsampling,
-                           encoder_decoder_fusion)
+                           encoder_decoder_fusion, activation)
 
         self.temp = temp
         self.gate_layer = GlobalGate(branch_num=5)
@@ -246,7 +244,7 @@ class SkipGateESANet(nn.Module):
         er, ed = self.encoder_rgb, self.encoder_depth
         if self.training:
             ops.begin_step()
-        if ops.stem_bn_fuse_supported((rgb.shape[2] + 1) // 2, (rgb.shape[3] + 1) // 2, er.bn1, ed.bn1):
+        if ops.stem_bn_fuse_supported((rgb.shape[2] + 1) // 2, (rgb.shape[3] + 1) // 2, er.bn1, ed.bn1, self.activation):
             # training: stem BatchNorm + ReLU are applied on load by the fusion / pooling kernels (never written)
             c_r, c_d = er.conv1, ed.conv1
             # (bn_stats: the batch statistics of bn1 come out of the stem convolution's epilogue where the kernel can;
@@ -272,10 +270,10 @@ class SkipGateESANet(nn.Module):
         d = ed.forward_first_conv(depth)
         if ops.se_fuse_pool_supported(r):
             # stem fusion (always on) + both max-pools as one pass; the full-resolution fused map is never written
-            r, d = ops.se_fuse_pool(r, d, self._se(0))
+            r, d = ops.se_fuse_pool(r, d, self._se(0), se_act=self.activation)
         else:
             d, d_pool = ops.fan_out(d, 2)                           # depth stem output: stem fusion + its own max-pool
-            fuse = ops.se_fuse_blend(r, d, self._se(0))
+            fuse = ops.se_fuse_blend(r, d, self._se(0), se_act=self.activation)
             r = ops.max_pool_3x3_s2(fuse)
             d = ops.max_pool_3x3_s2(d_pool)
         return r, d
@@ -371,7 +369,7 @@ class SkipGateESANet(nn.Module):
                     else:
                         r = getattr(er, f'forward_layer{j}')(r_in)
                         d = getattr(ed, f'forward_layer{j}')(d_in)
-                    fuse = ops.se_fuse_blend(r, d, self._se(j), wc, j - 1, inplace=True)
+                    fuse = ops.se_fuse_blend(r, d, self._se(j), wc, j - 1, inplace=True, se_act=self.activation)
                 else:
                     r = getattr(er, f'forward_layer{j}')(r_in)
                     fuse, d = r, None                # every sample skips depth from here on
@@ -389,7 +387,7 @@ class SkipGateESANet(nn.Module):
                 if j < 4:
                     d_f, d = ops.fan_out(d, 2)       # stage-j depth features: fusion + next depth stage
                 # stage j<4: w*rgb + (1-w)*fused with w = sum_{k<j} weight[:,k];  stage 4: w = 1-weight[:,4]
-                fuse = ops.se_fuse_blend(r, d_f, self._se(j), wcs[j - 1], j - 1)
+                fuse = ops.se_fuse_blend(r, d_f, self._se(j), wcs[j - 1], j - 1, se_act=self.activation)
                 if j < 4 and self.encoder_decoder_fusion == 'add':
                     fuse, f_skip = ops.fan_out(fuse, 2)   # fused map: next RGB stage + decoder skip connection
                     skips.append(decoder_skip(self, j, f_skip))

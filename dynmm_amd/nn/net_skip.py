@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .blocks import ResNetEncoder
+from .blocks import ResNetEncoder, normalize_activation
 from .fusion import SqueezeAndExciteFusionAdd, SqueezeAndExciteReweigh
 from .net import build_decoder_side, check_decoder_options, decoder_skip, encoder_stage_pair
 
@@ -33,16 +33,14 @@ class SkipESANet(nn.Module):
         super().__init__()
         channels_decoder = [128, 128, 128] if channels_decoder is None else list(channels_decoder)
         nr_decoder_blocks = [1, 1, 1] if nr_decoder_blocks is None else list(nr_decoder_blocks)
-        if activation.lower() != 'relu':
-            raise NotImplementedError('Only relu is implemented as activation on the HIP path. '
-                                      'Got {}'.format(activation))
+        self.activation = activation = normalize_activation(activation)      # 'relu' | 'swish' | 'hswish'
         check_decoder_options(upsampling, encoder_decoder_fusion)
         self.fuse_depth_in_rgb_encoder = fuse_depth_in_rgb_encoder
         self.block_rule = block_rule if block_rule else [1, 1, 1, 1]
         self.height, self.width = height, width
 
-        self.encoder_rgb = ResNetEncoder(encoder_rgb, encoder_block, input_channels=3)
-        self.encoder_depth = ResNetEncoder(encoder_depth, encoder_block, input_channels=1)
+        self.encoder_rgb = ResNetEncoder(encoder_rgb, encoder_block, input_channels=3, activation=activation)
+        self.encoder_depth = ResNetEncoder(encoder_depth, encoder_block, input_channels=1, activation=activation)
         if pretrained_on_imagenet:                    # resnet.py:395-509, local files only (loud when absent)
             from ..src.pretrained import load_imagenet_encoder
             load_imagenet_encoder(self.encoder_rgb, encoder_rgb, encoder_block, 3, pretrained_dir)
@@ -56,14 +54,14 @@ class SkipESANet(nn.Module):
             # constructed (and checkpointed) by the reference but never used by its forward
             # (model_skip_mod.py:113-130 vs :235-311) — kept for state_dict parity only
             for j, ch in enumerate(stage_ch):
-                setattr(self, f'se_layer{j}', SqueezeAndExciteFusionAdd(ch))
+                setattr(self, f'se_layer{j}', SqueezeAndExciteFusionAdd(ch, activation=activation))
 
         self.temp = temp
         for j in range(4):
-            setattr(self, f'gate_layer{j}', SqueezeAndExciteReweigh(self.temp, stage_ch[j]))
+            setattr(self, f'gate_layer{j}', SqueezeAndExciteReweigh(self.temp, stage_ch[j], activation=activation))
 
         build_decoder_side(self, channels_decoder, nr_decoder_blocks, num_classes, context_module, upsampling,
-                           encoder_decoder_fusion)
+                           encoder_decoder_fusion, activation)
 
         self.hard_gate = False
         self.ini_stage = False
@@ -89,7 +87,9 @@ class SkipESANet(nn.Module):
         self.save_weight_info = True
         self.weight_list = [torch.Tensor() for _ in range(4)]
 
-    def end_weight(self, print_each=False, thre=None):
+    def end_weight(self, print_each=False, thre=None, print_flop=False):
+        """(print_flop: accepted and ignored — the drivers end every model's weight recording with the same call, and this
+        network has no FLOP table to print; model_skip_mod.py:219-233)"""
         self.save_weight_info = False
         avg = []
         for i in range(4):
@@ -122,7 +122,7 @@ class SkipESANet(nn.Module):
         else:
             noise = None if self.gumbel_noise is None else self.gumbel_noise[j]
             fuse, w, aux = ops.reweigh_fuse(r, d, wblend, mode, gate.se.mlp_params(), gate.temp,
-                                            self.hard_gate or test, prev, noise)
+                                            self.hard_gate or test, prev, noise, se_act=self.activation)
             self.last_aux[j] = aux
         if self.save_weight_info and record:
             self.weight_list[j] = torch.cat((self.weight_list[j], w.detach().cpu()))
@@ -163,7 +163,8 @@ class SkipESANet(nn.Module):
                     noise = None if self.gumbel_noise is None else self.gumbel_noise[j]
                     if noise is not None and not full:
                         noise = noise[idx].contiguous()
-                    fused, w_a, _ = ops.reweigh_fuse(r_a, d, None, 1, gate.se.mlp_params(), gate.temp, True, None, noise)
+                    fused, w_a, _ = ops.reweigh_fuse(r_a, d, None, 1, gate.se.mlp_params(), gate.temp, True, None, noise,
+                                                       se_act=self.activation)
                     if full:
                         wj = w_a
                     else:

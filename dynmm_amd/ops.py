@@ -819,6 +819,61 @@ class PackedWeights:
         self.valid = False
 
 
+def _planes(t):
+    """(N, C, HW) view of a tensor for the plane-wise pointwise kernels"""
+    if t.dim() >= 2:
+        return t.shape[0], t.shape[1], max(t.numel() // max(t.shape[0] * t.shape[1], 1), 1)
+    return 1, max(t.numel(), 1), 1
+
+
+class _Activation(Function):
+    """a = act(z) with the backward through the saved PRE-activation z (csrc/norm.hip act_pre_*): the form Swish and Hswish need —
+    neither is invertible, so their derivative cannot be read off the output the way ReLU's and tanh's are (csrc/common.h)."""
+
+    @staticmethod
+    def forward(ctx, z, act):
+        z = _chk(z, 'z')
+        a = torch.empty_like(z)
+        if z.numel():
+            N, Cc, HW = _planes(z)
+            L.check(_lib().dynmm_act_pre_fwd(_p(z), _p(a), N, Cc, HW, act, _stream()), 'act_pre_fwd')
+        ctx.act = act
+        ctx.save_for_backward(z)
+        return a
+
+    @staticmethod
+    def backward(ctx, g):
+        z, = ctx.saved_tensors
+        g = _chk(g, 'grad')
+        dz = torch.empty_like(z)
+        if z.numel():
+            N, Cc, HW = _planes(z)
+            L.check(_lib().dynmm_act_pre_bwd(_p(g), _p(z), _p(dz), None, None, N, Cc, HW, ctx.act, _stream()), 'act_pre_bwd')
+        return dz, None
+
+
+def is_smooth(act):
+    """Swish / Hswish (any spelling lib.ACT knows): the activations whose backward needs the pre-activation, and which none of the
+    ReLU-decision fusions (deferred masks, BNLink, the bit masks, BatchNorm + ReLU on load in the stem) may take."""
+    return ACT[act] in L.SMOOTH_ACTS
+
+
+def activation(x, act):
+    """act(x), pointwise and differentiable, for every code of lib.ACT ('relu', 'tanh', 'swish' = 'silu', 'hswish', None).  The
+    backward saves x."""
+    code = ACT[act]
+    if code == L.ACT_NONE:
+        return x
+    if not (torch.is_grad_enabled() and x.requires_grad):
+        x = _chk(x, 'x')
+        a = torch.empty_like(x)
+        if x.numel():
+            N, Cc, HW = _planes(x)
+            L.check(_lib().dynmm_act_pre_fwd(_p(x), _p(a), N, Cc, HW, code, _stream()), 'act_pre_fwd')
+        return a
+    return _Activation.apply(x, code)
+
+
 class _Conv2d(Function):
     @staticmethod
     def forward(ctx, x, x2, weight, bias, stride, padding, act, mask_input, defer_mask, link, w_owner=None, stats=None,
@@ -1043,7 +1098,14 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, act=None, x2=None, mask_in
     bn_stats: the output goes straight into a training-mode batch_norm_act: where the forward kernel can, it leaves the BatchNorm's
     batch statistics with the output (`y._bn_sums`) and batch_norm_act skips its statistics pass.
     bn_link: x is the output of batch_norm_act(..., 'relu', bwd_link=bn_link) and this convolution is its only consumer — or, for a
-    BatchNorm with an identity branch, its only consumer besides the identity branch behind `link` (BNLink, both forms)."""
+    BatchNorm with an identity branch, its only consumer besides the identity branch behind `link` (BNLink, both forms).
+
+    act 'swish' / 'hswish' (training): the kernel writes the pre-activation and the pointwise kernel applies the activation
+    (`activation`: one more saved activation-sized tensor than ReLU); every ReLU-decision hint above is IGNORED — there is no
+    mask to defer or to apply — while `link`, which only adds a gradient, stays."""
+    if is_smooth(act) and (torch.is_grad_enabled() or not isinstance(weight, torch.nn.Parameter) or w_owner is not None):
+        z = conv2d(x, weight, bias, stride, padding, None, x2, link=link, w_owner=w_owner)
+        return activation(z, act)
     if not torch.is_grad_enabled() and isinstance(weight, torch.nn.Parameter) and w_owner is None:
         # inference: the packed weight is cached on the parameter (conv2d_fused_eval) instead of re-laid-out per call
         # (the factorised blocks' conv -> ReLU pairs were 83 pack launches per forward of config P)
@@ -1223,7 +1285,9 @@ class _BatchNormAct(Function):
             sums = pre_sums                      # left by the producing convolution's epilogue (conv2d(bn_stats=True))
         elif training:
             sums, zeroed = _zero_sums(2 * Cc, dev)
-            L.check(lib.dynmm_bn_stats(_p(x), _p(sums), N, Cc, HW, zeroed, st), 'bn_stats')
+            # (Swish / Hswish: squares in fp64 — csrc/norm.hip bn_stats_f64_kernel says why; ReLU keeps its kernel and its bits)
+            stats_fn = lib.dynmm_bn_stats_f64 if act in L.SMOOTH_ACTS else lib.dynmm_bn_stats
+            L.check(stats_fn(_p(x), _p(sums), N, Cc, HW, zeroed, st), 'bn_stats')
         mean = torch.empty(Cc, device=dev, dtype=torch.float32)
         invstd = torch.empty(Cc, device=dev, dtype=torch.float32)
         y = torch.empty_like(x)
@@ -1250,8 +1314,10 @@ class _BatchNormAct(Function):
         ctx.has_res = residual is not None
         # ReLU without residual: the backward re-derives the mask from x (bit-identical to this forward's
         # fma) instead of reading y — one tensor read less in bn_bwd_reduce and in bn_bwd_apply
-        need_y = act != L.ACT_NONE and not (act == L.ACT_RELU and residual is None) and bits is None
-        ctx.save_for_backward(x, y if need_y else None, gamma, mean, invstd, beta, bits)
+        # Swish / Hswish: the backward re-evaluates the pre-activation from x (+ the residual, saved IN y's SLOT: y is not needed)
+        smooth = act in L.SMOOTH_ACTS
+        need_y = act != L.ACT_NONE and not (act == L.ACT_RELU and residual is None) and bits is None and not smooth
+        ctx.save_for_backward(x, residual if smooth else (y if need_y else None), gamma, mean, invstd, beta, bits)
         ctx.g_param, ctx.b_param = gamma, beta
         return y
 
@@ -1261,6 +1327,8 @@ class _BatchNormAct(Function):
         st = _stream()
         x, y, gamma, mean, invstd, beta, bits = ctx.saved_tensors
         gy = _chk(gy, 'grad')
+        if ctx.act in L.SMOOTH_ACTS:
+            return _BatchNormAct._backward_pre(ctx, gy, x, y, gamma, mean, invstd, beta)       # (y's slot holds the residual)
         if bits is not None and gy.data_ptr() % 16 != 0:
             gy = gy.clone()                      # (a gradient view off the 16-byte grid: the bit path reads 16 bytes per lane)
         N, Cc, H, W = x.shape
@@ -1294,9 +1362,37 @@ class _BatchNormAct(Function):
         return dx, dgamma_ret, dbeta_ret, None, None, dres, None, None, None, None, None, None, None, None
 
 
+    @staticmethod
+    def _backward_pre(ctx, gy, x, res, gamma, mean, invstd, beta):
+        """Swish / Hswish: both passes re-evaluate z = BN(x) + residual with the forward's own fma and apply act'(z)."""
+        lib = _lib()
+        st = _stream()
+        N, Cc, H, W = x.shape
+        HW = H * W
+        sums, zeroed = _zero_sums(2 * Cc, x.device)
+        L.check(lib.dynmm_bn_bwd_reduce_pre(_p(gy), _p(x), _p(res), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(sums),
+                                            N, Cc, HW, ctx.act, zeroed, st), 'bn_bwd_reduce_pre')
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(x) if (ctx.has_res and ctx.needs_input_grad[5]) else None
+        dgamma, dgamma_ret = _grad_dst(ctx.g_param)
+        dbeta, dbeta_ret = _grad_dst(ctx.b_param)
+        L.check(lib.dynmm_bn_bwd_apply_pre(_p(gy), _p(x), _p(res), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(sums),
+                                           _p(dx), _p(dres), _p(dgamma), _p(dbeta), N, Cc, HW, int(ctx.training), ctx.act, st),
+                'bn_bwd_apply_pre')
+        if ctx.link is not None and dres is not None:
+            ctx.link.dres, dres = dres, None      # absorbed by the first conv's dgrad epilogue (activation-independent)
+        _grads_enqueued()
+        return dx, dgamma_ret, dbeta_ret, None, None, dres, None, None, None, None, None, None, None, None
+
+
 def batch_norm_act(x, bn, act=None, residual=None, training=None, link=None, bwd_link=None):
     """act(BatchNorm2d(x) + residual) using the parameters/buffers of the nn.BatchNorm2d `bn`.
-    `link`: GradLink that carries the residual's gradient to the op that consumes the same tensor."""
+    `link`: GradLink that carries the residual's gradient to the op that consumes the same tensor.
+
+    Batch statistics (training): taken from `x._bn_sums` when the producing convolution left them (fp32 squares, every
+    activation); otherwise by a pass of this op — with fp32 squares for act None / 'relu' / 'tanh' (unchanged, bit for bit) and
+    with fp64 squares for 'swish' / 'hswish' (dynmm_bn_stats_f64).  So the same x can give statistics that differ in the last
+    bits depending on `act`: a precision increase scoped to the new path, not a property of the activation."""
     training = bn.training if training is None else training
     nbt = bn.num_batches_tracked if training else None       # incremented inside the normalise kernel
     if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
@@ -1590,7 +1686,7 @@ class _SEFuseBlend(Function):
     only) writes the prefix into rgb's own storage, so skipped samples cost no memory traffic at all."""
 
     @staticmethod
-    def forward(ctx, rgb, depth, wcum, col, use_se, inplace, *params):
+    def forward(ctx, rgb, depth, wcum, col, use_se, inplace, se_act, *params):
         lib = _lib()
         st = _stream()
         rgb, depth = _chk(rgb, 'rgb'), _chk(depth, 'depth')
@@ -1616,8 +1712,8 @@ class _SEFuseBlend(Function):
             hr, hd = torch.empty((n_act, Cc // 16), **f32), torch.empty((n_act, Cc // 16), **f32)
             gr, gd = torch.empty((n_act, Cc), **f32), torch.empty((n_act, Cc), **f32)
         a, b = torch.empty((n_act, Cc), **f32), torch.empty((n_act, Cc), **f32)
-        L.check(lib.dynmm_se_coeff_fwd(_p(sr), _p(sd), parr, wc_ptr, wc_stride, _p(a), _p(b),
-                                       _p(hr), _p(hd), _p(gr), _p(gd), n_act, Cc, int(use_se), st), 'se_coeff_fwd')
+        L.check(lib.dynmm_se_coeff_fwd_act(_p(sr), _p(sd), parr, wc_ptr, wc_stride, _p(a), _p(b),
+                                           _p(hr), _p(hd), _p(gr), _p(gd), n_act, Cc, int(use_se), se_act, st), 'se_coeff_fwd')
         if inplace and n_act < N:
             out = rgb                                   # prefix overwritten below, tail untouched
             ctx.mark_dirty(rgb)
@@ -1626,6 +1722,7 @@ class _SEFuseBlend(Function):
             _copy_rows(rgb, out, n_act, N - n_act)
         L.check(lib.dynmm_axpby_fwd(_p(rgb), _p(depth), _p(a), _p(b), _p(out), n_act * Cc, HW, st), 'axpby_fwd')
         ctx.use_se = use_se
+        ctx.se_act = se_act
         ctx.col = col
         ctx.n_params = len(params)
         ctx.param_objs = list(params)
@@ -1662,15 +1759,15 @@ class _SEFuseBlend(Function):
                 dwcum = torch.zeros_like(wcum)           # samples past n_act: no gate gradient from this stage
                 dwc_ptr = dwcum.data_ptr() + 4 * ctx.col
         ws = torch.empty(lib.dynmm_se_coeff_bwd_workspace_bytes(n_act, Cc) // 4, **f32) if ctx.use_se else None
-        L.check(lib.dynmm_se_coeff_bwd(_p(da), _p(db), _p(sr), _p(sd), parr, wc_ptr, wc_stride,
-                                       _p(hr), _p(hd), _p(gr), _p(gd), dparr, _p(dsr), _p(dsd),
-                                       dwc_ptr, wc_stride, _p(ws), n_act, Cc, int(ctx.use_se), st), 'se_coeff_bwd')
+        L.check(lib.dynmm_se_coeff_bwd_act(_p(da), _p(db), _p(sr), _p(sd), parr, wc_ptr, wc_stride,
+                                           _p(hr), _p(hd), _p(gr), _p(gd), dparr, _p(dsr), _p(dsd),
+                                           dwc_ptr, wc_stride, _p(ws), n_act, Cc, int(ctx.use_se), ctx.se_act, st), 'se_coeff_bwd')
         drgb, ddepth = torch.empty_like(rgb), torch.empty_like(depth)
         L.check(lib.dynmm_axpby_bwd_apply(_p(g), _p(a), _p(b), _p(dsr), _p(dsd), 1.0 / HW,
                                           _p(drgb), _p(ddepth), n_act * Cc, HW, st), 'axpby_bwd_apply')
         _copy_rows(g, drgb, n_act, N - n_act)            # skipped samples: out = rgb
         _grads_enqueued()
-        return (drgb, ddepth, dwcum, None, None, None, *dparams_ret)
+        return (drgb, ddepth, dwcum, None, None, None, None, *dparams_ret)
 
 
 class _SEFusePool(Function):
@@ -1678,7 +1775,7 @@ class _SEFusePool(Function):
     …globalgate.py:258-261 without ever writing the full-resolution fused map (csrc/pointwise.hip: axpby_pool_*)."""
 
     @staticmethod
-    def forward(ctx, rgb, depth, use_se, *params):
+    def forward(ctx, rgb, depth, use_se, se_act, *params):
         lib = _lib()
         st = _stream()
         rgb, depth = _chk(rgb, 'rgb'), _chk(depth, 'depth')
@@ -1696,8 +1793,9 @@ class _SEFusePool(Function):
             hr, hd = torch.empty((N, Cc // 16), **f32), torch.empty((N, Cc // 16), **f32)
             gr, gd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
         a, b = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-        L.check(lib.dynmm_se_coeff_fwd(_p(sr), _p(sd), parr, None, 0, _p(a), _p(b), _p(hr), _p(hd), _p(gr), _p(gd),
-                                       N, Cc, int(use_se), st), 'se_coeff_fwd')
+        L.check(lib.dynmm_se_coeff_fwd_act(_p(sr), _p(sd), parr, None, 0, _p(a), _p(b), _p(hr), _p(hd), _p(gr), _p(gd),
+                                           N, Cc, int(use_se), se_act, st), 'se_coeff_fwd')
+        ctx.se_act = se_act
         Ho, Wo = H // 2, W // 2
         yo, yd = torch.empty((N, Cc, Ho, Wo), **f32), torch.empty((N, Cc, Ho, Wo), **f32)
         io = torch.empty((N, Cc, Ho, Wo), device=rgb.device, dtype=torch.int8)
@@ -1733,13 +1831,14 @@ class _SEFusePool(Function):
             parr, dparr = _ptr_array(params), _ptr_array(dparams)
             dsr, dsd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
         ws = torch.empty(lib.dynmm_se_coeff_bwd_workspace_bytes(N, Cc) // 4, **f32) if ctx.use_se else None
-        L.check(lib.dynmm_se_coeff_bwd(_p(da), _p(db), _p(sr), _p(sd), parr, None, 0, _p(hr), _p(hd), _p(gr), _p(gd),
-                                       dparr, _p(dsr), _p(dsd), None, 0, _p(ws), N, Cc, int(ctx.use_se), st), 'se_coeff_bwd')
+        L.check(lib.dynmm_se_coeff_bwd_act(_p(da), _p(db), _p(sr), _p(sd), parr, None, 0, _p(hr), _p(hd), _p(gr), _p(gd),
+                                           dparr, _p(dsr), _p(dsd), None, 0, _p(ws), N, Cc, int(ctx.use_se), ctx.se_act, st),
+                'se_coeff_bwd')
         drgb, ddepth = torch.empty_like(rgb), torch.empty_like(depth)
         L.check(lib.dynmm_axpby_pool_bwd_apply(_p(g_o), io.data_ptr(), _p(g_d), idd.data_ptr(), _p(a), _p(b), _p(dsr), _p(dsd),
                                                1.0 / HW, _p(drgb), _p(ddepth), N * Cc, H, W, st), 'axpby_pool_bwd_apply')
         _grads_enqueued()
-        return (drgb, ddepth, None, *dparams_ret)
+        return (drgb, ddepth, None, None, *dparams_ret)
 
 
 class _StemBNFusePool(Function):
@@ -1924,9 +2023,9 @@ _FUSED_STEM_POOL = True        # (module attributes: tests compare the fused ste
 _FUSED_STEM_BN = True
 
 
-def stem_bn_fuse_supported(h, w, bn_a, bn_b):
-    """h, w: spatial size of the stem conv outputs"""
-    return _FUSED_STEM_BN and _FUSED_STEM_POOL and bool(_lib().dynmm_axpby_pool_supported(int(h), int(w))) and \
+def stem_bn_fuse_supported(h, w, bn_a, bn_b, act='relu'):
+    """h, w: spatial size of the stem conv outputs.  The fused stem tail applies BatchNorm + ReLU on load: ReLU only."""
+    return ACT[act] == L.ACT_RELU and _FUSED_STEM_BN and _FUSED_STEM_POOL and bool(_lib().dynmm_axpby_pool_supported(int(h), int(w))) and \
         bn_a.training and bn_b.training and torch.is_grad_enabled() and bn_a.momentum is not None and \
         bn_b.momentum is not None
 
@@ -1936,18 +2035,20 @@ def se_fuse_pool_supported(x):
     return _FUSED_STEM_POOL and x.dim() == 4 and bool(_lib().dynmm_axpby_pool_supported(int(x.shape[2]), int(x.shape[3])))
 
 
-def se_fuse_pool(rgb, depth, se_params=None):
-    """(max_pool_3x3_s2(se_fuse_blend(rgb, depth, se_params)), max_pool_3x3_s2(depth)) in one forward pass."""
+def se_fuse_pool(rgb, depth, se_params=None, se_act='relu'):
+    """(max_pool_3x3_s2(se_fuse_blend(rgb, depth, se_params)), max_pool_3x3_s2(depth)) in one forward pass.
+    se_act: the hidden activation of the two excitation MLPs."""
     use_se = se_params is not None
-    return _SEFusePool.apply(rgb, depth, use_se, *(tuple(se_params) if use_se else ()))
+    return _SEFusePool.apply(rgb, depth, use_se, ACT[se_act], *(tuple(se_params) if use_se else ()))
 
 
-def se_fuse_blend(rgb, depth, se_params=None, wcum=None, col=0, inplace=False):
+def se_fuse_blend(rgb, depth, se_params=None, wcum=None, col=0, inplace=False, se_act='relu'):
     """se_params: None ('add' fusion) or the 8 tensors (W1r,b1r,W2r,b2r,W1d,b1d,W2d,b2d).
-    depth may hold only a PREFIX of rgb's batch (compaction): the remaining samples pass rgb through."""
+    depth may hold only a PREFIX of rgb's batch (compaction): the remaining samples pass rgb through.
+    se_act: the hidden activation of the two excitation MLPs (model_utils.py:36-51 builds them with the network's)."""
     use_se = se_params is not None
     params = tuple(se_params) if use_se else ()
-    return _SEFuseBlend.apply(rgb, depth, wcum, col, use_se, bool(inplace) and not torch.is_grad_enabled(), *params)
+    return _SEFuseBlend.apply(rgb, depth, wcum, col, use_se, bool(inplace) and not torch.is_grad_enabled(), ACT[se_act], *params)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1973,7 +2074,7 @@ class _ReweighFuse(Function):
     aux   = [N,6] saved gate internals {w, ysoft0, ysoft1, y1, E0, E1} (not differentiable)."""
 
     @staticmethod
-    def forward(ctx, rgb, depth, wblend, prev, noise, blend_mode, gate, temp, hard, *params):
+    def forward(ctx, rgb, depth, wblend, prev, noise, blend_mode, gate, temp, hard, se_act, *params):
         lib = _lib()
         st = _stream()
         rgb, depth = _chk(rgb, 'rgb'), _chk(depth, 'depth')
@@ -1997,9 +2098,10 @@ class _ReweighFuse(Function):
                 seed, offset = _PHILOX_SEED, _PHILOX_OFFSET[0]
                 _PHILOX_OFFSET[0] += 1
         a, b = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-        L.check(lib.dynmm_reweigh_fwd(_p(sr), _p(sd), parr, _p(wblend), int(blend_mode), _p(prev), 1, _p(noise),
-                                      seed, offset, float(temp), int(bool(hard)), _p(a), _p(b), _p(wnext),
-                                      _p(h), _p(gg), _p(aux), N, Cc, st), 'reweigh_fwd')
+        L.check(lib.dynmm_reweigh_fwd_act(_p(sr), _p(sd), parr, _p(wblend), int(blend_mode), _p(prev), 1, _p(noise),
+                                          seed, offset, float(temp), int(bool(hard)), _p(a), _p(b), _p(wnext),
+                                          _p(h), _p(gg), _p(aux), N, Cc, se_act, st), 'reweigh_fwd')
+        ctx.se_act = se_act
         out = torch.empty_like(rgb)
         L.check(lib.dynmm_axpby_fwd(_p(rgb), _p(depth), _p(a), _p(b), _p(out), N * Cc, HW, st), 'axpby_fwd')
         ctx.cfg = (int(blend_mode), bool(gate), float(temp), len(params))
@@ -2042,18 +2144,18 @@ class _ReweighFuse(Function):
                 d_prev = torch.empty((N,), **f32)
         if need_wb or gate_bwd:
             ws = torch.empty(lib.dynmm_reweigh_bwd_workspace_bytes(N, Cc) // 4, **f32) if gate_bwd else None
-            L.check(lib.dynmm_reweigh_bwd(_p(d_wnext) if gate_bwd else None, _p(da), _p(db), _p(sr), _p(sd), parr,
-                                          _p(prev), 1, _p(h), _p(gg), _p(aux), dparr, _p(dsr), _p(dsd),
-                                          _p(d_wblend), _p(d_prev), _p(ws), temp, N, Cc, st), 'reweigh_bwd')
+            L.check(lib.dynmm_reweigh_bwd_act(_p(d_wnext) if gate_bwd else None, _p(da), _p(db), _p(sr), _p(sd), parr,
+                                              _p(prev), 1, _p(h), _p(gg), _p(aux), dparr, _p(dsr), _p(dsd),
+                                              _p(d_wblend), _p(d_prev), _p(ws), temp, N, Cc, ctx.se_act, st), 'reweigh_bwd')
         drgb, ddepth = torch.empty_like(rgb), torch.empty_like(depth)
         L.check(lib.dynmm_axpby_bwd_apply(_p(g), _p(a), _p(b), _p(dsr), _p(dsd), 1.0 / HW,
                                           _p(drgb), _p(ddepth), N * Cc, HW, st), 'axpby_bwd_apply')
         _grads_enqueued()
-        return (drgb, ddepth, d_wblend, d_prev, None, None, None, None, None, *dparams_ret)
+        return (drgb, ddepth, d_wblend, d_prev, None, None, None, None, None, None, *dparams_ret)
 
 
 def reweigh_fuse(rgb, depth, wblend=None, blend_mode=1, gate_params=None, temp=1.0, hard=False, prev=None,
-                 noise=None):
+                 noise=None, se_act='relu'):
     """One SkipESANet fusion point (model_skip_mod.py:235-311): the stage blend and, when `gate_params`
     (W1,b1,W2,b2 of SqueezeAndExcitationWeight.fc) is given, the gate evaluated on the same two maps.
     Returns (fused, wnext[N,2] | None, aux | None).  `noise` = Exp(1) samples [N,2] (tests); default: the
@@ -2062,7 +2164,7 @@ def reweigh_fuse(rgb, depth, wblend=None, blend_mode=1, gate_params=None, temp=1
     params = tuple(gate_params) if gate else ()
     if prev is not None and not prev.is_contiguous():
         prev = prev.contiguous()
-    return _ReweighFuse.apply(rgb, depth, wblend, prev, noise, blend_mode, gate, temp, hard, *params)
+    return _ReweighFuse.apply(rgb, depth, wblend, prev, noise, blend_mode, gate, temp, hard, ACT[se_act], *params)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -34,6 +34,14 @@ extern "C" {
 #define DYNMM_ACT_NONE 0
 #define DYNMM_ACT_RELU 1
 #define DYNMM_ACT_TANH 2
+/* The smooth activations of the reference's --activation flag (model_utils.py:100-115).  Neither is invertible, so their
+ * backward passes take the PRE-activation z (dynmm_act_pre_*, dynmm_bn_bwd_*_pre, the *_act SE entry points); the entry
+ * points that express act' through the OUTPUT (dynmm_act_bwd_bias, dynmm_bn_bwd_reduce / _apply) refuse them
+ * (DYNMM_EUNSUPPORTED).  The forward convolution epilogues and dynmm_bn_apply take them like ReLU and tanh.
+ *   SWISH : z * sigmoid(z)           d/dz = s * (1 + z * (1 - s)),  s = sigmoid(z)
+ *   HSWISH: z * relu6(z + 3) / 6     d/dz = 0 (z <= -3), (2 z + 3) / 6 (-3 < z < 3), 1 (z >= 3)   [torch's convention] */
+#define DYNMM_ACT_SWISH 3
+#define DYNMM_ACT_HSWISH 4
 
 #define DYNMM_LOSS_BCE_LOGITS 0   /* dynmm_head_loss kinds */
 #define DYNMM_LOSS_L1 1
@@ -240,11 +248,23 @@ size_t dynmm_act_bwd_bias_workspace_bytes(int N, int C);
 int dynmm_act_bwd_bias(const float* g, const float* y, float* g_out, float* dbias, float* workspace,
                        int N, int C, int HW, int act, void* stream);
 
+/* Pointwise activation on [N,C,HW] planes, every code above:  a = act(z)  (a may alias z), and its backward THROUGH THE
+ * PRE-ACTIVATION  dz = g * act'(z)  (dz may alias g; dz or dbias may be NULL, not both) with the per-channel
+ * dbias[c] = sum_{n,hw} dz summed over sample splits through `workspace` (>= dynmm_act_bwd_bias_workspace_bytes(N, C)) in a
+ * fixed order.  16-byte accesses when HW % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise. */
+int dynmm_act_pre_fwd(const float* z, float* a, int N, int C, int HW, int act, void* stream);
+int dynmm_act_pre_bwd(const float* g, const float* z, float* dz, float* dbias, float* workspace,
+                      int N, int C, int HW, int act, void* stream);
+
 /* ---- BatchNorm2d (src/models/resnet.py:59,110; model_utils.py:22; …globalgate.py:381,384) ---- */
 /* per-channel sum / sum of squares over (N,HW) into sums[2*C] (double).  sums_are_zero != 0: the caller
  * hands in a buffer that is already zero (e.g. a slice of an arena cleared once per step) and the memset
  * launch is skipped. */
 int dynmm_bn_stats(const float* x, double* sums, int N, int C, int HW, int sums_are_zero, void* stream);
+/* The same sums with each element widened to fp64 before it is squared (dynmm_bn_stats squares in fp32): for channels whose
+ * spread is small against their mean, E[x^2] - mu^2 otherwise loses the variance to the rounding of the squares.  Used by the
+ * BatchNorm + Swish / Hswish path. */
+int dynmm_bn_stats_f64(const float* x, double* sums, int N, int C, int HW, int sums_are_zero, void* stream);
 /* y = act( (x-mean)*invstd*gamma + beta + residual ).
  * training=k>=1: mean/var from `sums` [k][2][C] — k slabs added in slab order (1: dynmm_bn_stats; the slots of
  *             dynmm_conv2d_wino_fwd_stats) — (biased var for normalisation); writes save_mean/save_invstd[C],
@@ -284,6 +304,16 @@ int dynmm_bn_bwd_apply(const float* g, const float* y, const float* x,
                        const double* sums, float* dx, float* d_residual,
                        float* dgamma, float* dbeta,
                        int N, int C, int HW, int training, int act, const unsigned long long* relu_bits, void* stream);
+/* The two backward passes for ANY activation code, through the pre-activation: z = fma(x, gamma*invstd, fma(-mean,
+ * gamma*invstd, beta)) + residual is RE-EVALUATED from the saved convolution output x with dynmm_bn_apply's own expression
+ * (so the forward saves no activation-sized tensor besides x and the residual it was handed), g_eff = g * act'(z).
+ * residual may be NULL; everything else as dynmm_bn_bwd_reduce / dynmm_bn_bwd_apply. */
+int dynmm_bn_bwd_reduce_pre(const float* g, const float* x, const float* residual, const float* mean, const float* invstd,
+                            const float* gamma, const float* beta, double* sums, int N, int C, int HW, int act,
+                            int sums_are_zero, void* stream);
+int dynmm_bn_bwd_apply_pre(const float* g, const float* x, const float* residual, const float* mean, const float* invstd,
+                           const float* gamma, const float* beta, const double* sums, float* dx, float* d_residual,
+                           float* dgamma, float* dbeta, int N, int C, int HW, int training, int act, void* stream);
 /* eval-mode folding for the fused conv epilogue: scale = gamma*rsqrt(var+eps),
  * shift = beta + (conv_bias - mean)*scale   (conv_bias optional). */
 int dynmm_bn_fold(const float* gamma, const float* beta, const float* running_mean,
@@ -356,6 +386,18 @@ int dynmm_se_coeff_bwd(const float* da, const float* db, const float* sr, const 
                        const float* hr, const float* hd, const float* gr, const float* gd,
                        float* const* dparams, float* dsr, float* dsd, float* dwc, int dwc_stride,
                        float* workspace, int N, int C, int use_se, void* stream);
+/* The same pair with the hidden activation as an argument (the two above are act = DYNMM_ACT_RELU).  For the smooth codes
+ * hr / hd hold the hidden PRE-activation W1 s + b1 (ReLU: the post-activation, as above) — pass the forward's buffers and
+ * the forward's `act` to the backward. */
+int dynmm_se_coeff_fwd_act(const float* sr, const float* sd, const float* const* params,
+                           const float* wc, int wc_stride, float* a, float* b,
+                           float* hr, float* hd, float* gr, float* gd,
+                           int N, int C, int use_se, int act, void* stream);
+int dynmm_se_coeff_bwd_act(const float* da, const float* db, const float* sr, const float* sd,
+                           const float* const* params, const float* wc, int wc_stride,
+                           const float* hr, const float* hd, const float* gr, const float* gd,
+                           float* const* dparams, float* dsr, float* dsd, float* dwc, int dwc_stride,
+                           float* workspace, int N, int C, int use_se, int act, void* stream);
 /* out = a[n,c]*xr + b[n,c]*xd */
 int dynmm_axpby_fwd(const float* xr, const float* xd, const float* a, const float* b, float* out,
                     int NC, int HW, void* stream);
@@ -425,6 +467,18 @@ int dynmm_reweigh_bwd(const float* d_wnext, const float* da, const float* db, co
                       const float* h, const float* g, const float* aux, float* const* dparams,
                       float* dsr, float* dsd, float* d_wblend, float* d_prev, float* workspace, float temp,
                       int N, int C, void* stream);
+/* The same pair with the hidden activation of the gate's excitation as an argument (above: DYNMM_ACT_RELU); h holds the
+ * hidden pre-activation for the smooth codes, as dynmm_se_coeff_fwd_act's. */
+int dynmm_reweigh_fwd_act(const float* sr, const float* sd, const float* const* params,
+                          const float* wblend, int blend_mode, const float* prev, int prev_stride,
+                          const float* noise, unsigned long long seed, unsigned long long offset,
+                          float temp, int hard, float* a, float* b, float* wnext, float* h, float* g,
+                          float* aux, int N, int C, int act, void* stream);
+int dynmm_reweigh_bwd_act(const float* d_wnext, const float* da, const float* db, const float* sr,
+                          const float* sd, const float* const* params, const float* prev, int prev_stride,
+                          const float* h, const float* g, const float* aux, float* const* dparams,
+                          float* dsr, float* dsd, float* d_wblend, float* d_prev, float* workspace, float temp,
+                          int N, int C, int act, void* stream);
 
 /* ---- global gate head (…globalgate.py:20-30, 263-272, 314-315, 391-394) ----
  * mode 0: logits = fc[5,J] . pooled[n,J];  weight = DiffSoftmax(logits, temp, hard)
