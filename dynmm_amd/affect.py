@@ -216,7 +216,9 @@ def build_model(args):
 def main(argv=None):
     args = parser().parse_args(argv)
     if args.enc != 'transformer':
-        raise NotImplementedError(f'--enc {args.enc}: only the transformer encoders run on the HIP path (no GRU kernels)')
+        raise NotImplementedError(f'--enc {args.enc}: the driver switch is not wired yet (only the transformer experts are '
+                                  f'gated from the command line); the gru experts themselves run on the HIP path: '
+                                  f'dynmm_amd.nn.affect.GRU, experts.affect_uni_gru / affect_mm_gru')
     torch.cuda.set_device(args.gpu)
     device = torch.device('cuda', args.gpu)
     loaders = load_data(args, device)

@@ -19,6 +19,8 @@ File contract (state_dicts, read with strict=True by imdb.load_pretrained and af
   imdb_mm --fuse 1 / 0     best_lf.pt / best_ef.pt
   affect_uni --mod 0/1/2   reg_transformer_{encoder,head}_{visual,audio,text}.pt; text also b1_reg_transformer_{encoder,head}_text.pt
   affect_mm --fusion 3     lf_tran.pt and b2_lf_tran.pt
+  affect_uni_gru(mod)      reg_gru_{encoder,head}_{visual,audio,text}.pt      (builders: the command-line switches --enc gru /
+  affect_mm_gru(1 / 0)     lf_gru.pt / ef_gru.pt                               --fusion 0 | 1 are not wired yet)
 The b1_ / b2_ copies are the names affect_dyn.py:211 (`--model v2`) reads, which a reference user makes by renaming.
 """
 import copy
@@ -42,12 +44,7 @@ PATIENCE = 7                 # Supervised_Learning.train: `if early_stop and pat
 # ---------------------------------------------------------------------------------------------------------------------
 # experts
 # ---------------------------------------------------------------------------------------------------------------------
-class Identity(nn.Module):
-    """MultiBench unimodals.common_models.Identity."""
-
-    def forward(self, x):
-        return x
-
+Identity = A.Identity        # MultiBench unimodals.common_models.Identity
 
 IMDB_MODS = ('text', 'image')
 A_MODS = ('visual', 'audio', 'text')
@@ -83,7 +80,9 @@ def imdb_mm(fuse):
 def affect_uni(mod, enc='transformer', hidden_dim1=0, hidden_dim2=0, clf=False):
     """affect_uni.py: (encoder, head, modality name) of modality `mod` (0 visual, 1 audio, 2 text)."""
     if enc != 'transformer':
-        raise NotImplementedError(f'--enc {enc}: the GRU encoder has no HIP kernels (only --enc transformer runs)')
+        raise NotImplementedError(f'--enc {enc}: the driver switch is not wired yet (only --enc transformer runs from the '
+                                  f'command line); the GRU expert itself runs on the HIP path: dynmm_amd.nn.affect.GRU, '
+                                  f'experts.affect_uni_gru')
     if clf:
         raise NotImplementedError('--clf: the 2-output posneg-clf head trains with CrossEntropyLoss, which has no HIP '
                                   'objective kernel (only the regression head with L1Loss runs)')
@@ -99,15 +98,45 @@ def affect_mm(fusion):
     """affect_mm.py: the MMDL of `--fusion` (3: late-fusion transformers, DynMMNetV2's branch2)."""
     if fusion == 3:
         return A.late_fusion_transformer()
-    if fusion in (0, 1, 5):
-        raise NotImplementedError(f'affect_mm --fusion {fusion} ({AFFECT_FUSION[fusion]}): its GRU encoders have no HIP '
-                                  f'kernels')
+    if fusion in (0, 1):
+        raise NotImplementedError(f'affect_mm --fusion {fusion} ({AFFECT_FUSION[fusion]}): the driver switch is not wired yet; '
+                                  f'the GRU model itself runs on the HIP path: dynmm_amd.nn.affect.GRU, '
+                                  f'experts.affect_mm_gru')
+    if fusion == 5:
+        raise NotImplementedError('affect_mm --fusion 5 (lrtf): LowRankTensorFusion over GRUWithLinear encoders has no HIP '
+                                  'kernels')
     if fusion == 4:
         raise NotImplementedError('affect_mm --fusion 4 (mult): MULTModel has no HIP kernels')
     if fusion == 2:
         raise NotImplementedError('affect_mm --fusion 2 (ef_tran): the early-fusion Transformer(409, 300) head is not built '
                                   'on the HIP path')
     raise ValueError(f'--fusion {fusion}: one of 0-5')
+
+
+GRU_DIMS = {0: (64, 32), 1: (128, 64), 2: (512, 256)}        # affect_uni.py:38-60 (`--enc gru`): (hidden_dim1, hidden_dim2)
+
+
+def affect_uni_gru(mod, hidden_dim1=0, hidden_dim2=0):
+    """affect_uni.py `--enc gru`: (GRU encoder, MLP head, modality name) of modality `mod` (0 visual, 1 audio, 2 text); saved
+    as reg_gru_{encoder,head}_{name}.pt (affect_uni.file_names)."""
+    if mod not in (0, 1, 2):
+        raise ValueError(f'--mod {mod}: 0 (visual), 1 (audio) or 2 (text)')
+    name = A_MODS[mod]
+    h1 = hidden_dim1 if hidden_dim1 > 0 else GRU_DIMS[mod][0]
+    h2 = hidden_dim2 if hidden_dim2 > 0 else GRU_DIMS[mod][1]
+    return A.GRU(A.FEATURES[name], h1, dropout=True, has_padding=True), A.MLP(h1, h2, 1), name
+
+
+def affect_mm_gru(fusion):
+    """affect_mm.py `--fusion 1` (lf_gru: three GRUs, Concat, MLP(704, 512, 1); lf_gru.pt) and `--fusion 0` (ef_gru: Identity
+    encoders, ConcatEarly, Sequential(GRU(409, 512), MLP(512, 256, 1)); ef_gru.pt)."""
+    if fusion == 1:
+        return A.late_fusion_gru()
+    if fusion == 0:
+        return A.early_fusion_gru()
+    if fusion == 5:
+        raise NotImplementedError('affect_mm --fusion 5 (lrtf): LowRankTensorFusion has no HIP kernels')
+    raise ValueError(f'affect_mm_gru({fusion}): 0 (ef_gru) or 1 (lf_gru)')
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -124,6 +153,13 @@ def _leaves(x):
     if isinstance(x, (list, tuple)):
         return [t for v in x for t in _leaves(v)]
     return [x] if torch.is_tensor(x) and x.is_cuda else []
+
+
+def _host_leaves(x):
+    """is any leaf of the nested lists x not a device tensor?"""
+    if isinstance(x, (list, tuple)):
+        return any(_host_leaves(v) for v in x)
+    return not (torch.is_tensor(x) and x.is_cuda)
 
 
 class ExpertTrainStep(engine.FlatAdamWStep):
@@ -160,6 +196,11 @@ class ExpertTrainStep(engine.FlatAdamWStep):
         return (tuple(tuple(t.shape) for t in _leaves(inputs)), tuple(target.shape), bool(self.model.training))
 
     def _clone_inputs(self, inputs):
+        # (called once per capture) a GRU reads its padding lengths on the device: host lengths would be uploaded inside the
+        # capture and frozen into it
+        if any(isinstance(m, A.GRU) and m.has_padding for m in self.model.modules()) and _host_leaves(inputs[1]):
+            raise ValueError('ExpertTrainStep(use_graph=True) on a GRU expert: pass the padding lengths as device tensors (host '
+                             'lengths would be frozen into the capture)')
         return _map(inputs, lambda t: t.clone())
 
     _input_tensors = staticmethod(_leaves)

@@ -186,6 +186,12 @@ SIGNATURES = {
     'dynmm_ml_partition': (c_i, [c_f, c_i, c_i, c_f, c_f, c_f, c_f]),
     'dynmm_posneg_counts': (c_i, [c_f, c_i, c_f, c_i, c_f, C.c_double, c_i, c_f, c_f, c_f]),
     'dynmm_head_loss': (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
+    'dynmm_gru_packed_floats': (c_sz, [c_i]),
+    'dynmm_gru_pack': (c_i, [c_f, c_f, c_i, c_f]),
+    'dynmm_gru_arm': (c_i, [c_i, c_i, c_i]),
+    'dynmm_gru_bwd_workspace_bytes': (c_sz, [c_i, c_i]),
+    'dynmm_gru_seq_fwd': (c_i, [c_f] * 7 + [c_i] * 4 + [c_f]),
+    'dynmm_gru_seq_bwd': (c_i, [c_f] * 9 + [c_sz] + [c_i] * 4 + [c_f]),
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 

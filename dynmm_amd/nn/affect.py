@@ -9,8 +9,12 @@ MultiBench's published definitions:
                                  nn.TransformerEncoder(nn.TransformerEncoderLayer(d_model=dim, nhead=5), num_layers=5)
                                  (post-norm, ReLU, dim_feedforward 2048), output = the LAST time step.  The padding
                                  lengths that accompany the input are ignored (`x = x[0]`).
+  GRU(indim, hiddim, ...)        nn.GRU(indim, hiddim, batch_first=True); has_padding: h_n of the packed [x, lengths];
+                                 last_only: the last step; else the sequence; then Dropout(dropoutp) and flatten.  Unlike the
+                                 transformer a GRU has an exact yardstick: torch.nn.GRU in float64 (tests/test_gru.py).
   MLP(indim, hiddim, outdim)     fc -> ReLU -> fc2
   Concat                         torch.cat(..., dim=1)
+  ConcatEarly                    torch.cat(..., dim=2)
   MMDL(encoders, fusion, head)   head(fusion([enc_i([x_i, len_i])]))          (Supervised_Learning.py:16-51 — vendored)
 
 and, from the reference's own file, DynMMNetV2 (affect_dyn.py:107-175: expert 1 = text Transformer + MLP head,
@@ -152,13 +156,64 @@ class MLP(nn.Module):
         return S.linear_bdt(S.linear_bdt(x, self.fc.weight, self.fc.bias, act='relu'), self.fc2.weight, self.fc2.bias)
 
 
+class GRU(nn.Module):
+    """MultiBench unimodals.common_models.GRU.  `self.gru` is torch's nn.GRU as a PARAMETER CONTAINER (state_dict keys
+    gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0); its forward is never called: the input projection is
+    the 1x1-convolution GEMM, the recurrence csrc/gru.hip (ops_seq.gru_seq).  The dropout site is named 'gru_dropout'."""
+
+    def __init__(self, indim, hiddim, dropout=False, dropoutp=0.1, flatten=False, has_padding=False, last_only=False,
+                 batch_first=True):
+        super().__init__()
+        if not batch_first:
+            raise NotImplementedError('GRU(batch_first=False): the reference only builds batch-first GRUs')
+        self.gru = nn.GRU(indim, hiddim, batch_first=True)
+        self.dropout = dropout
+        self.dropout_layer = nn.Dropout(dropoutp)
+        self.flatten, self.has_padding, self.last_only, self.batch_first = flatten, has_padding, last_only, batch_first
+        self.arm = None               # (tests: 'resident' | 'stepped' forces a dispatch arm)
+        self._site = S.new_sites(1)
+
+    def forward(self, x):
+        g = self.gru
+        w = (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)
+        if self.has_padding:
+            out, _ = S.gru_seq(x[0], *w, lengths=x[1], arm=self.arm)
+        else:
+            hn, seq = S.gru_seq(x, *w, arm=self.arm)
+            out = hn if self.last_only else seq
+        if self.dropout and self.training:
+            out = S.dropout_bdt(out, self.dropout_layer.p, self._site, 'gru_dropout')
+        if self.flatten:
+            out = torch.flatten(out, 1)
+        return out
+
+
+class Identity(nn.Module):
+    """MultiBench unimodals.common_models.Identity."""
+
+    def forward(self, x):
+        return x
+
+
+class Sequential(nn.Sequential):
+    """MultiBench unimodals.common_models.Sequential: nn.Sequential whose first layer may take [x, lengths]."""
+
+
+class ConcatEarly(nn.Module):
+    """MultiBench fusions.common_fusions.ConcatEarly: the modalities side by side along the feature axis of [B, T, F]."""
+
+    def forward(self, modalities):
+        return torch.cat(modalities, dim=2)
+
+
 class Concat(nn.Module):
     def forward(self, modalities):
         return torch.cat([m.flatten(1) for m in modalities], dim=1)
 
 
 class MMDL(nn.Module):
-    """Supervised_Learning.py:16-51 with has_padding=True and tensor-valued encoders."""
+    """Supervised_Learning.py:16-51.  With has_padding, encoders that return [x, lengths] (Identity under ConcatEarly) have
+    their tensors fused and the head receives [fused, lengths of modality 0]."""
 
     def __init__(self, encoders, fusion, head, has_padding=True):
         super().__init__()
@@ -166,12 +221,31 @@ class MMDL(nn.Module):
         self.fuse, self.head, self.has_padding = fusion, head, has_padding
 
     def forward(self, inputs):
-        return self.head(self.fuse(run_branches(self.branch_fns(inputs))))
+        fns = self.branch_fns(inputs)
+        # (Identity encoders launch nothing: no side streams for them)
+        outs = [f() for f in fns] if all(isinstance(e, Identity) for e in self.encoders) else run_branches(fns)
+        if self.has_padding and not torch.is_tensor(outs[0]):
+            out = self.head([self.fuse([o[0] for o in outs]), inputs[1][0]])
+        else:
+            out = self.head(self.fuse(outs))
+        return out[0] if type(out) is list else out
 
     def branch_fns(self, inputs):
         if self.has_padding:
             return [lambda i=i, enc=enc: enc([inputs[0][i], inputs[1][i]]) for i, enc in enumerate(self.encoders)]
         return [lambda i=i, enc=enc: enc(inputs[i]) for i, enc in enumerate(self.encoders)]
+
+
+def late_fusion_gru():
+    """affect_mm.py:45-55 (`--fusion 1`, saved as lf_gru.pt)."""
+    return MMDL([GRU(35, 64, dropout=True, has_padding=True), GRU(74, 128, dropout=True, has_padding=True),
+                 GRU(300, 512, dropout=True, has_padding=True)], Concat(), MLP(704, 512, 1))
+
+
+def early_fusion_gru():
+    """affect_mm.py:40-44 (`--fusion 0`, saved as ef_gru.pt)."""
+    return MMDL([Identity(), Identity(), Identity()], ConcatEarly(),
+                Sequential(GRU(409, 512, dropout=True, has_padding=True), MLP(512, 256, 1)))
 
 
 def late_fusion_transformer():

@@ -299,6 +299,96 @@ def ffn_block(h, layer, drop_f, drop2):
                            layer.norm2.weight, layer.norm2.bias, layer.norm2.eps, df, d2)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# GRU (MultiBench unimodals.common_models.GRU: torch.nn.GRU, one layer, one direction, h0 = 0), csrc/gru.hip
+# ---------------------------------------------------------------------------------------------------------------
+GRU_ARMS = {None: 0, 0: 0, 'auto': 0, 1: 1, 'resident': 1, 2: 2, 'stepped': 2}
+GRU_ARM_NAMES = {1: 'resident', 2: 'stepped'}
+
+
+def gru_arm(B, H, T):
+    """the dispatch arm ('resident' | 'stepped') the library picks for this shape"""
+    return GRU_ARM_NAMES[_lib().dynmm_gru_arm(int(B), int(H), int(T))]
+
+
+def gru_lengths(lengths, device):
+    """lengths (device tensor, host tensor or list) as the device int32 [B] the kernels read.  Host lengths are uploaded per
+    call; while the stream is capturing that would freeze them into the capture, so they are refused."""
+    if lengths is None:
+        return None
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        return lengths if lengths.dtype == torch.int32 and lengths.is_contiguous() else lengths.to(torch.int32).contiguous()
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise ValueError('GRU: host lengths under a stream capture would be frozen into it; pass them as a device tensor')
+    return torch.as_tensor(lengths, dtype=torch.int32).to(device)
+
+
+class _GRUCore(Function):
+    """The recurrence over gi [T, 3H, B] (time = the convolution's batch axis): (h_n [H, B], states [T, H, B])."""
+
+    @staticmethod
+    def forward(ctx, gi, w_hh, b_hh, lengths, arm):
+        lib = _lib()
+        gi, w, b = _chk(gi, 'gi'), _chk(w_hh.detach(), 'weight_hh'), _chk(b_hh.detach(), 'bias_hh')
+        T, H3, B = gi.shape
+        H = H3 // 3
+        if tuple(w.shape) != (3 * H, H) or tuple(b.shape) != (3 * H,) or H3 != 3 * H:
+            raise L.DynmmHipError(f'gru: gi {tuple(gi.shape)}, weight_hh {tuple(w.shape)}, bias_hh {tuple(b.shape)} do not agree')
+        if lengths is not None and (lengths.dtype != torch.int32 or not lengths.is_cuda or lengths.numel() != B):
+            raise L.DynmmHipError(f'gru: lengths must be {B} int32 values on the device')
+        f32 = dict(device=gi.device, dtype=torch.float32)
+        st = _stream()
+        packed = torch.empty(lib.dynmm_gru_packed_floats(H), **f32)
+        L.check(lib.dynmm_gru_pack(_p(w), _p(packed), H, st), 'gru_pack')
+        hbuf = torch.empty((T + 1, H, B), **f32)
+        gates = torch.empty((T, 4 * H, B), **f32)
+        hn = torch.empty((H, B), **f32)
+        L.check(lib.dynmm_gru_seq_fwd(_p(gi), _p(packed), _p(b), _p(lengths), _p(hbuf), _p(gates), _p(hn), T, B, H, arm, st),
+                'gru_seq_fwd')
+        ctx.save_for_backward(packed, hbuf, gates)
+        ctx.lengths, ctx.arm, ctx.params = lengths, arm, (w_hh, b_hh)
+        ctx.set_materialize_grads(False)
+        return hn, hbuf[1:]
+
+    @staticmethod
+    def backward(ctx, d_hn, d_hseq):
+        lib = _lib()
+        packed, hbuf, gates = ctx.saved_tensors
+        T, H, B = hbuf.shape[0] - 1, hbuf.shape[1], hbuf.shape[2]
+        if d_hn is None and d_hseq is None:
+            return None, None, None, None, None
+        d_hn, d_hseq = _chk(d_hn, 'grad'), _chk(d_hseq, 'grad')
+        f32 = dict(device=hbuf.device, dtype=torch.float32)
+        dgi, dgh = torch.empty((T, 3 * H, B), **f32), torch.empty((T, 3 * H, B), **f32)
+        nb = lib.dynmm_gru_bwd_workspace_bytes(B, H)
+        ws = torch.empty(nb // 4, **f32)
+        L.check(lib.dynmm_gru_seq_bwd(_p(d_hn), _p(d_hseq), _p(packed), _p(ctx.lengths), _p(hbuf), _p(gates), _p(dgi), _p(dgh),
+                                      _p(ws), nb, T, B, H, ctx.arm, _stream()), 'gru_seq_bwd')
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            # dW_hh / db_hh: the 1x1-convolution weight gradient of (previous states, dgh), time as the batch axis
+            dw, db = _wgrad_1x1(hbuf[:T], dgh, *ctx.params)
+        return (dgi if ctx.needs_input_grad[0] else None), (dw if ctx.needs_input_grad[1] else None), \
+            (db if ctx.needs_input_grad[2] else None), None, None
+
+
+def gru_seq(x, w_ih, w_hh, b_ih, b_hh, lengths=None, arm=None):
+    """torch.nn.GRU (one layer, one direction, batch_first, h0 = 0) on x [B, T, F]: (h_n [B, H], h_seq [B, T, H] or None).
+    lengths (device int32 [B], host tensor or list, each in 1..T): sample b runs lengths[b] steps and h_n is its state at
+    t = lengths[b] - 1 (`gru(pack_padded_sequence(x, lengths, enforce_sorted=False))[1][-1]`); no sequence is returned.
+    arm: None (the library decides, `gru_arm`) | 'resident' | 'stepped'."""
+    if arm not in GRU_ARMS:
+        raise ValueError(f'arm must be one of None, "resident", "stepped", got {arm!r}')
+    x = _chk(x, 'x')
+    if x.dim() != 3:
+        raise L.DynmmHipError(f'gru: x must be [B, T, F], got {tuple(x.shape)}')
+    lengths = gru_lengths(lengths, x.device)
+    gi = linear_bdt(x.permute(1, 2, 0).contiguous(), w_ih, b_ih)         # [T, 3H, B]: every step one contiguous slab
+    train_w = torch.is_grad_enabled() and (w_hh.requires_grad or b_hh.requires_grad)
+    hn, hseq = _GRUCore.apply(gi, w_hh if train_w else w_hh.detach(), b_hh if train_w else b_hh.detach(), lengths, GRU_ARMS[arm])
+    return hn.t().contiguous(), (None if lengths is not None else hseq.permute(2, 0, 1).contiguous())
+
+
 class _MHACore(Function):
     @staticmethod
     def forward(ctx, qkv, heads, drop=None):

@@ -711,6 +711,35 @@ int dynmm_posneg_counts(const float* out, int out_stride, const float* y, int B,
 int dynmm_head_loss(const float* out, const float* target, int B, int C, int kind, float* loss, float* d_out,
                     double* loss_acc, void* stream);
 
+/* ---- the GRU experts of the modality-level DynMM (MultiBench unimodals.common_models.GRU: affect_uni.py --enc gru,
+ * affect_mm.py --fusion 0 / 1), csrc/gru.hip ----
+ * The recurrence of torch.nn.GRU with one layer, one direction and h0 = 0 (gate order r | z | n):
+ *   r = sigmoid(gi_r + W_hr h + b_hr), z = sigmoid(gi_z + W_hz h + b_hz), n = tanh(gi_n + r (W_hn h + b_hn)),
+ *   h' = (1 - z) n + z h,
+ * where gi = W_ih x + b_ih of all time steps is a 1x1 convolution (dynmm_conv2d_fwd) the caller runs first.  Time is the
+ * convolution's batch axis: gi [T, 3H, B], hbuf [T + 1, H, B] (slab 0 = h0 = zeros, written by the call; slab t + 1 = the state
+ * after step t), gates [T, 4H, B] (r | z | n | W_hn h + b_hn, kept for the backward), hn [H, B].  lengths (optional, DEVICE
+ * int32 [B], each in 1..T): sample b updates while t < lengths[b] and holds its state afterwards, so hn is the state at
+ * t = lengths[b] - 1 (pack_padded_sequence); NULL: every sample runs T steps.  Any H >= 1 (<= 4096).
+ * packed = dynmm_gru_pack(W_hh [3H, H]): dynmm_gru_packed_floats(H) floats, W_hh and its transpose in the MFMA operand order, H
+ * padded to a multiple of 16 with zeros.
+ * arm: 0 = dynmm_gru_arm(B, H, T) decides, 1 = resident (one launch for the sequence, state in LDS; H <= 512, else
+ * DYNMM_EUNSUPPORTED), 2 = stepped (one launch per time step; under a capture: T kernel nodes).  Both arms compute the same
+ * function; the order of the fp32 sums over the hidden units differs.
+ * bwd: d_hn [H, B] and / or d_hseq [T, H, B] (the gradient of hbuf's slabs 1..T; either may be NULL, not both) ->
+ * dgi [T, 3H, B] (the gradient of gi) and dgh [T, 3H, B] (of W_hh h + b_hh: dgi with its n block times r); masked steps are
+ * written as zeros.  dW_hh / db_hh are the 1x1-convolution weight gradient of (hbuf slabs 0..T-1, dgh): dynmm_conv2d_wgrad.
+ * workspace: dynmm_gru_bwd_workspace_bytes(B, H), used by the stepped arm only (NULL allowed for arm 1). */
+size_t dynmm_gru_packed_floats(int H);
+int dynmm_gru_pack(const float* w_hh, float* packed, int H, void* stream);
+int dynmm_gru_arm(int B, int H, int T);
+size_t dynmm_gru_bwd_workspace_bytes(int B, int H);
+int dynmm_gru_seq_fwd(const float* gi, const float* packed, const float* b_hh, const int* lengths, float* hbuf, float* gates,
+                      float* hn, int T, int B, int H, int arm, void* stream);
+int dynmm_gru_seq_bwd(const float* d_hn, const float* d_hseq, const float* packed, const int* lengths, const float* hbuf,
+                      const float* gates, float* dgi, float* dgh, float* workspace, size_t workspace_bytes, int T, int B, int H,
+                      int arm, void* stream);
+
 /* ---- NYUv2 input pipeline (FusionDynMM/src/preprocessing.py), csrc/rgbd_aug.hip ---- */
 /* One batch of network inputs from decoded samples kept on the device: rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit,
  * label [S,H0,W0] uint8.  params [N,8] int32 per output sample: {stored index, th, tw, mode, ci, cj, flip, 0}: the stored sample
