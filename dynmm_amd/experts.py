@@ -21,6 +21,8 @@ File contract (state_dicts, read with strict=True by imdb.load_pretrained and af
   affect_mm --fusion 3     lf_tran.pt and b2_lf_tran.pt
   affect_uni_gru(mod)      reg_gru_{encoder,head}_{visual,audio,text}.pt      (builders: the command-line switches --enc gru /
   affect_mm_gru(1 / 0)     lf_gru.pt / ef_gru.pt                               --fusion 0 | 1 are not wired yet)
+  imdb_mm_lrtf()           best_lrtf.pt                                       (builders: --fuse 2 / --fusion 5 are not wired
+  affect_mm_lrtf()         lrtf.pt                                             yet)
 The b1_ / b2_ copies are the names affect_dyn.py:211 (`--model v2`) reads, which a reference user makes by renaming.
 """
 import copy
@@ -60,6 +62,13 @@ def imdb_uni(mod):
     return enc, I.MLP(512, 512, I.NUM_CLASSES)
 
 
+def _tag_maxout(model):
+    for name, m in model.named_modules():
+        if isinstance(m, I.MaxOut_MLP):
+            m.tag = name                         # dropout sites named after the module path (tests inject masks by name)
+    return model
+
+
 def imdb_mm(fuse):
     """imdb_mm.py: the MMDL of `--fuse` (1: late fusion, DynMMNet's branch3; 0: early fusion) and its learning rate."""
     if fuse in (0, 1):
@@ -67,14 +76,17 @@ def imdb_mm(fuse):
             model, lr = I.late_fusion_maxout(), 8e-3
         else:
             model, lr = I.MMDL([Identity(), Identity()], I.Concat(), I.MaxOut_MLP(I.NUM_CLASSES, 512, 4396)), 4e-2
-        for name, m in model.named_modules():
-            if isinstance(m, I.MaxOut_MLP):
-                m.tag = name                     # dropout sites named after the module path (tests inject masks by name)
-        return model, lr
+        return _tag_maxout(model), lr
     if fuse in (2, 3):
         missing = 'LowRankTensorFusion' if fuse == 2 else 'MultiplicativeInteractions2Modal'
         raise NotImplementedError(f'imdb_mm --fuse {fuse} ({IMDB_FUSE[fuse]}): {missing} has no HIP kernels')
     raise ValueError(f'--fuse {fuse}: one of 0-3')
+
+
+def imdb_mm_lrtf(rank=128):
+    """imdb_mm.py `--fuse 2` (lrtf: two MaxOut_MLPs, LowRankTensorFusion([512, 512], 512, 128), Linear(512, 23); best_lrtf.pt
+    through imdb_mm.file_name(dir, 2)) and its learning rate."""
+    return _tag_maxout(I.low_rank_fusion_maxout(rank)), 8e-3
 
 
 def affect_uni(mod, enc='transformer', hidden_dim1=0, hidden_dim2=0, clf=False):
@@ -139,6 +151,12 @@ def affect_mm_gru(fusion):
     raise ValueError(f'affect_mm_gru({fusion}): 0 (ef_gru) or 1 (lf_gru)')
 
 
+def affect_mm_lrtf(rank=32):
+    """affect_mm.py `--fusion 5` (lrtf: three GRUWithLinear encoders, LowRankTensorFusion([32, 32, 128], 128, 32),
+    MLP(128, 512, 1); lrtf.pt through affect_mm.file_names(dir, 5))."""
+    return A.low_rank_fusion_gru(rank)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # train step
 # ---------------------------------------------------------------------------------------------------------------------
@@ -198,7 +216,8 @@ class ExpertTrainStep(engine.FlatAdamWStep):
     def _clone_inputs(self, inputs):
         # (called once per capture) a GRU reads its padding lengths on the device: host lengths would be uploaded inside the
         # capture and frozen into it
-        if any(isinstance(m, A.GRU) and m.has_padding for m in self.model.modules()) and _host_leaves(inputs[1]):
+        grus = (A.GRU, A.GRUWithLinear)
+        if any(isinstance(m, grus) and m.has_padding for m in self.model.modules()) and _host_leaves(inputs[1]):
             raise ValueError('ExpertTrainStep(use_graph=True) on a GRU expert: pass the padding lengths as device tensors (host '
                              'lengths would be frozen into the capture)')
         return _map(inputs, lambda t: t.clone())

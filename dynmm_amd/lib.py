@@ -38,6 +38,7 @@ class Dropout(C.Structure):
 _GP = C.POINTER(ConvGeom)
 _DP = C.POINTER(Dropout)
 _PP = C.POINTER(C.c_void_p)
+_IP = C.POINTER(C.c_int)
 
 # name -> (restype, argtypes); mirrors include/dynmm_hip.h one to one
 SIGNATURES = {
@@ -192,6 +193,10 @@ SIGNATURES = {
     'dynmm_gru_bwd_workspace_bytes': (c_sz, [c_i, c_i]),
     'dynmm_gru_seq_fwd': (c_i, [c_f] * 7 + [c_i] * 4 + [c_f]),
     'dynmm_gru_seq_bwd': (c_i, [c_f] * 9 + [c_sz] + [c_i] * 4 + [c_f]),
+    'dynmm_lrtf_fwd_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
+    'dynmm_lrtf_fwd': (c_i, [_PP, _PP, _IP, c_i, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_f]),
+    'dynmm_lrtf_bwd_workspace_bytes': (c_sz, [c_i, _IP, c_i, c_i, c_i]),
+    'dynmm_lrtf_bwd': (c_i, [c_f, _PP, _PP, _IP, c_i, c_f, _PP, _PP, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_f]),
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 

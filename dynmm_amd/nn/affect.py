@@ -12,8 +12,14 @@ MultiBench's published definitions:
   GRU(indim, hiddim, ...)        nn.GRU(indim, hiddim, batch_first=True); has_padding: h_n of the packed [x, lengths];
                                  last_only: the last step; else the sequence; then Dropout(dropoutp) and flatten.  Unlike the
                                  transformer a GRU has an exact yardstick: torch.nn.GRU in float64 (tests/test_gru.py).
+  GRUWithLinear(indim, hiddim, outdim, ...)
+                                 nn.GRU(indim, hiddim) then nn.Linear(hiddim, outdim); has_padding: h_n of the packed [x, lengths]
+                                 (batch-first), Dropout, linear; else the linear layer on the whole state sequence
   MLP(indim, hiddim, outdim)     fc -> ReLU -> fc2
   Concat                         torch.cat(..., dim=1)
+  LowRankTensorFusion(input_dims, output_dim, rank)
+                                 factors[m] [rank, d_m + 1, out], fusion_weights [1, rank], fusion_bias [1, out]:
+                                 sum_r w[r] prod_m ([1 | z_m] factors[m][r]) + bias      
   ConcatEarly                    torch.cat(..., dim=2)
   MMDL(encoders, fusion, head)   head(fusion([enc_i([x_i, len_i])]))          (Supervised_Learning.py:16-51 — vendored)
 
@@ -188,6 +194,69 @@ class GRU(nn.Module):
         return out
 
 
+class GRUWithLinear(nn.Module):
+    """MultiBench unimodals.common_models.GRUWithLinear: nn.GRU(indim, hiddim) (a parameter container, as in GRU above) followed by
+    nn.Linear(hiddim, outdim); state_dict keys gru.*, linear.weight, linear.bias.  has_padding: h_n of the packed [x, lengths]
+    (batch-first) -> Dropout -> linear, [B, outdim]; else the linear layer on the whole state sequence of x [B, T, F],
+    [B, T, outdim].  The dropout site is named 'gru_dropout'."""
+
+    def __init__(self, indim, hiddim, outdim, dropout=False, dropoutp=0.1, flatten=False, has_padding=False):
+        super().__init__()
+        self.gru = nn.GRU(indim, hiddim)
+        self.linear = nn.Linear(hiddim, outdim)
+        self.dropout = dropout
+        self.dropout_layer = nn.Dropout(dropoutp)
+        self.flatten, self.has_padding = flatten, has_padding
+        self.arm = None               # (tests: 'resident' | 'stepped' forces a dispatch arm)
+        self._site = S.new_sites(1)
+
+    def forward(self, x):
+        g = self.gru
+        w = (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)
+        if self.has_padding:
+            hidden, _ = S.gru_seq(x[0], *w, lengths=x[1], arm=self.arm)          # [B, H]
+        else:
+            hidden = S.gru_seq(x, *w, arm=self.arm)[1]                           # [B, T, H]
+        if self.dropout and self.training:
+            hidden = S.dropout_bdt(hidden, self.dropout_layer.p, self._site, 'gru_dropout')
+        if hidden.dim() == 3:
+            out = S.linear_bdt(hidden.permute(0, 2, 1).contiguous(), self.linear.weight, self.linear.bias)
+            out = out.permute(0, 2, 1).contiguous()
+        else:
+            out = S.linear_bdt(hidden, self.linear.weight, self.linear.bias)
+        if self.flatten:
+            out = torch.flatten(out, 1)
+        return out
+
+
+class LowRankTensorFusion(nn.Module):
+    """MultiBench fusions.common_fusions.LowRankTensorFusion(input_dims, output_dim, rank, flatten=True) on ops_seq.lrtf.  The
+    factors, fusion_weights and fusion_bias are REGISTERED parameters (keys factors.0, factors.1, ..., fusion_weights,
+    fusion_bias): MultiBench's `nn.Parameter(...).to(device)` leaves them out of parameters() and state_dict() on a GPU."""
+
+    def __init__(self, input_dims, output_dim, rank, flatten=True):
+        super().__init__()
+        if not flatten:
+            raise NotImplementedError('LowRankTensorFusion(flatten=False): the reference only builds flatten=True')
+        if len(input_dims) not in (2, 3):
+            raise NotImplementedError(f'LowRankTensorFusion over {len(input_dims)} modalities: the HIP kernels serve 2 or 3')
+        self.input_dims, self.output_dim, self.rank, self.flatten = list(input_dims), output_dim, rank, flatten
+        self.factors = nn.ParameterList(
+            [nn.Parameter(nn.init.xavier_normal_(torch.empty(rank, d + 1, output_dim))) for d in input_dims])
+        self.fusion_weights = nn.Parameter(nn.init.xavier_normal_(torch.empty(1, rank)))
+        self.fusion_bias = nn.Parameter(torch.zeros(1, output_dim))
+        self._register_state_dict_hook(self._factors_first)
+
+    @staticmethod
+    def _factors_first(module, state_dict, prefix, local_metadata):
+        # the keys in the order the module creates its tensors (a ParameterList is a child module: torch lists it last)
+        for k in ('fusion_weights', 'fusion_bias'):
+            state_dict.move_to_end(prefix + k)
+
+    def forward(self, modalities):
+        return S.lrtf([m.flatten(1) for m in modalities], list(self.factors), self.fusion_weights, self.fusion_bias)
+
+
 class Identity(nn.Module):
     """MultiBench unimodals.common_models.Identity."""
 
@@ -240,6 +309,13 @@ def late_fusion_gru():
     """affect_mm.py:45-55 (`--fusion 1`, saved as lf_gru.pt)."""
     return MMDL([GRU(35, 64, dropout=True, has_padding=True), GRU(74, 128, dropout=True, has_padding=True),
                  GRU(300, 512, dropout=True, has_padding=True)], Concat(), MLP(704, 512, 1))
+
+
+def low_rank_fusion_gru(rank=32):
+    """affect_mm.py:88-93 (`--fusion 5`, saved as lrtf.pt)."""
+    kw = dict(dropout=True, has_padding=True)
+    return MMDL([GRUWithLinear(35, 64, 32, **kw), GRUWithLinear(74, 128, 32, **kw), GRUWithLinear(300, 512, 128, **kw)],
+                LowRankTensorFusion([32, 32, 128], 128, rank), MLP(128, 512, 1))
 
 
 def early_fusion_gru():

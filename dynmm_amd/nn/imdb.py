@@ -14,6 +14,7 @@ nor pinned to a commit (imdb_dyn.py:10-13).  The modules below restate MultiBenc
                                   op4 = Sequential(BatchNorm1d(second_hidden), Dropout(0.3)),
                                   hid2val = Linear(second_hidden, num_outputs) or None (linear_layer=False)
   Concat                          cat([m.flatten(1)], 1)
+  LowRankTensorFusion             nn.affect.LowRankTensorFusion (one class for both data sets)
   MMDL(encoders, fusion, head)    head(fusion([enc_i(x_i)]))   (has_padding=False)
 
 and, from the reference's own file, DynMMNet (imdb_dyn.py:29-114): expert 1 = text MLP encoder + MLP head, expert 2 =
@@ -37,7 +38,7 @@ import torch.nn as nn
 from .. import engine, ops
 from .. import ops_mlp as M
 from .. import ops_seq as S
-from .affect import join_branches, run_branches
+from .affect import LowRankTensorFusion, join_branches, run_branches     # noqa: F401 (LowRankTensorFusion: one class)
 
 NUM_CLASSES = 23
 FEATURES = {'text': 300, 'image': 4096}
@@ -131,6 +132,12 @@ def late_fusion_maxout():
     """imdb_mm.py --fuse 1 (saved as best_lf.pt): the third expert of DynMMNet."""
     return MMDL([MaxOut_MLP(512, 512, 300, linear_layer=False), MaxOut_MLP(512, 1024, 4096, 512, False)], Concat(),
                 Linear(1024, NUM_CLASSES))
+
+
+def low_rank_fusion_maxout(rank=128):
+    """imdb_mm.py:43-47 (`--fuse 2`, saved as best_lrtf.pt)."""
+    return MMDL([MaxOut_MLP(512, 512, 300, linear_layer=False), MaxOut_MLP(512, 1024, 4096, 512, False)],
+                LowRankTensorFusion([512, 512], 512, rank), Linear(512, NUM_CLASSES))
 
 
 class DynMMNet(nn.Module):

@@ -389,6 +389,104 @@ def gru_seq(x, w_ih, w_hh, b_ih, b_hh, lengths=None, arm=None):
     return hn.t().contiguous(), (None if lengths is not None else hseq.permute(2, 0, 1).contiguous())
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# low-rank tensor fusion (MultiBench fusions.common_fusions.LowRankTensorFusion), csrc/lrtf.hip
+# ---------------------------------------------------------------------------------------------------------------
+def _lrtf_operand(t, name, shape=None):
+    """a device, float32, contiguous operand (refused otherwise: the gradients are written in the operands' own layout)"""
+    if not torch.is_tensor(t):
+        raise L.DynmmHipError(f'lrtf: {name} must be a tensor, got {type(t).__name__}')
+    _chk(t, name)
+    if not t.is_contiguous():
+        raise L.DynmmHipError(f'lrtf: {name} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}')
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise L.DynmmHipError(f'lrtf: {name} must be {tuple(shape)}, got {tuple(t.shape)}')
+    return t
+
+
+class _LRTF(Function):
+    """out [B, O] of (fusion_weights [1, R], fusion_bias [1, O], z_0 .. z_{M-1}, F_0 .. F_{M-1}).  Saves its inputs only: the
+    backward recomputes every P_m."""
+
+    @staticmethod
+    def forward(ctx, w, bias, M, *zf):
+        lib = _lib()
+        zs, fs = zf[:M], zf[M:]
+        B, (R, _, O) = zs[0].shape[0], fs[0].shape
+        dims = (C.c_int * M)(*[z.shape[1] for z in zs])
+        st = _stream()
+        out = torch.empty((B, O), device=zs[0].device, dtype=torch.float32)
+        nb = lib.dynmm_lrtf_fwd_workspace_bytes(B, O, R)
+        ws = torch.empty(nb // 4, device=out.device, dtype=torch.float32) if nb else None
+        L.check(lib.dynmm_lrtf_fwd(_ptr_array(zs), _ptr_array(fs), dims, M, _p(w), _p(bias), _p(out), _p(ws), nb, B, O, R, st),
+                'lrtf_fwd')
+        ctx.M = M
+        ctx.save_for_backward(w, bias, *zf)
+        ctx.params = (w, bias) + tuple(fs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib()
+        M = ctx.M
+        w, bias = ctx.saved_tensors[:2]
+        zs, fs = ctx.saved_tensors[2:2 + M], ctx.saved_tensors[2 + M:]
+        g = _chk(g, 'grad')
+        B, (R, _, O) = zs[0].shape[0], fs[0].shape
+        dims = (C.c_int * M)(*[z.shape[1] for z in zs])
+        need = ctx.needs_input_grad
+        need_z = [need[3 + m] for m in range(M)]
+        need_p = need[0] or need[1] or any(need[3 + M:])
+        if not (need_p or any(need_z)):
+            return (None,) * (3 + 2 * M)
+        dzs = [torch.empty_like(z) if n else None for z, n in zip(zs, need_z)]
+        dz_arr = (C.c_void_p * M)(*[_p(t) for t in dzs])
+        dw_ret = db_ret = None
+        df_ret = [None] * M
+        dw = db = df_arr = None
+        if need_p:
+            # the fused backward produces the parameter gradients together: each lands in its parameter's slice of the flat
+            # gradient buffer (or in a fresh tensor under plain autograd)
+            pw, pb, pf = ctx.params[0], ctx.params[1], ctx.params[2:]
+            dw, dw_ret = _grad_dst(pw)
+            db, db_ret = _grad_dst(pb)
+            dfs = []
+            for m in range(M):
+                t, df_ret[m] = _grad_dst(pf[m])
+                dfs.append(t)
+            df_arr = _ptr_array(dfs)
+        nb = lib.dynmm_lrtf_bwd_workspace_bytes(M, dims, B, O, R)
+        ws = torch.empty(nb // 4, device=g.device, dtype=torch.float32)
+        L.check(lib.dynmm_lrtf_bwd(_p(g), _ptr_array(zs), _ptr_array(fs), dims, M, _p(w), dz_arr, df_arr, _p(dw), _p(db), _p(ws),
+                                   nb, B, O, R, _stream()), 'lrtf_bwd')
+        _grads_enqueued()
+        dw_ret = dw_ret if need[0] else None
+        db_ret = db_ret if need[1] else None
+        df_ret = [t if n else None for t, n in zip(df_ret, need[3 + M:])]
+        return (dw_ret, db_ret, None, *dzs, *df_ret)
+
+
+def lrtf(zs, factors, fusion_weights, fusion_bias):
+    """MultiBench's LowRankTensorFusion on M = 2 or 3 inputs z_m [B, d_m]: with P_m[r] = [1 | z_m] F_m[r] ([B, O]),
+    out = sum_r fusion_weights[0, r] prod_m P_m[r] + fusion_bias -> [B, O].  factors[m] [R, d_m + 1, O], fusion_weights [1, R],
+    fusion_bias [1, O].  One fused kernel forward, a recomputing backward (csrc/lrtf.hip); no [R, B, O] tensor exists."""
+    zs, factors = list(zs), list(factors)
+    M = len(zs)
+    if M not in (2, 3) or len(factors) != M:
+        raise L.DynmmHipError(f'lrtf: M = {M} inputs with {len(factors)} factors: the kernels serve M = 2 or 3 modalities, one '
+                              f'factor each')
+    zs = [_lrtf_operand(z, f'z[{m}]') for m, z in enumerate(zs)]
+    if any(z.dim() != 2 or z.shape[0] != zs[0].shape[0] for z in zs):
+        raise L.DynmmHipError(f'lrtf: inputs must be [B, d_m] with one B, got {[tuple(z.shape) for z in zs]}')
+    if factors[0].dim() != 3:
+        raise L.DynmmHipError(f'lrtf: factors[0] must be [R, d_0 + 1, O], got {tuple(factors[0].shape)}')
+    R, O = factors[0].shape[0], factors[0].shape[2]
+    factors = [_lrtf_operand(f, f'factors[{m}]', (R, zs[m].shape[1] + 1, O)) for m, f in enumerate(factors)]
+    w = _lrtf_operand(fusion_weights, 'fusion_weights', (1, R))
+    bias = _lrtf_operand(fusion_bias, 'fusion_bias', (1, O))
+    return _LRTF.apply(w, bias, M, *zs, *factors)
+
+
 class _MHACore(Function):
     @staticmethod
     def forward(ctx, qkv, heads, drop=None):

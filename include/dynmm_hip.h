@@ -740,6 +740,25 @@ int dynmm_gru_seq_bwd(const float* d_hn, const float* d_hseq, const float* packe
                       const float* gates, float* dgi, float* dgh, float* workspace, size_t workspace_bytes, int T, int B, int H,
                       int arm, void* stream);
 
+/* ---- low-rank tensor fusion (MultiBench fusions.common_fusions.LowRankTensorFusion: imdb_mm.py --fuse 2, affect_mm.py
+ * --fusion 5), csrc/lrtf.hip ----
+ *   P_m[r,b,o] = F_m[r,0,o] + sum_k z_m[b,k] F_m[r,k+1,o],   out[b,o] = sum_r w[r] prod_m P_m[r,b,o] + bias[o]
+ * zs / factors / dims: HOST arrays of M entries (device pointers z_m [B, dims[m]], F_m [R, dims[m] + 1, O]; the extents), w [R],
+ * bias [O], out [B, O]; all fp32, contiguous.  M = 2 or 3, anything else DYNMM_EUNSUPPORTED.  No [R, B, O] tensor is written:
+ * the P_m live in MFMA accumulators, and the backward recomputes them.  The ranks are split over workgroups where the output
+ * tiles alone would not fill the device; the partial outputs (fwd workspace) are then summed in a fixed order.
+ * bwd: g = the gradient of out.  dfs (HOST array of M device pointers, each like F_m) with dw [R] and dbias [O]: the parameter
+ * gradients, all of them or (dfs NULL) none.  dzs (HOST array of M device pointers like z_m; NULL entries, or dzs NULL, skip that
+ * input's work).  Gradients are OVERWRITTEN.  No floating-point atomics: equal inputs give equal bits.  The workspace holds the
+ * partial sums of dw and of the dz_m. */
+size_t dynmm_lrtf_fwd_workspace_bytes(int B, int O, int R);
+int dynmm_lrtf_fwd(const float* const* zs, const float* const* factors, const int* dims, int M, const float* w,
+                   const float* bias, float* out, float* workspace, size_t workspace_bytes, int B, int O, int R, void* stream);
+size_t dynmm_lrtf_bwd_workspace_bytes(int M, const int* dims, int B, int O, int R);
+int dynmm_lrtf_bwd(const float* g, const float* const* zs, const float* const* factors, const int* dims, int M, const float* w,
+                   float* const* dzs, float* const* dfs, float* dw, float* dbias, float* workspace, size_t workspace_bytes,
+                   int B, int O, int R, void* stream);
+
 /* ---- NYUv2 input pipeline (FusionDynMM/src/preprocessing.py), csrc/rgbd_aug.hip ---- */
 /* One batch of network inputs from decoded samples kept on the device: rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit,
  * label [S,H0,W0] uint8.  params [N,8] int32 per output sample: {stored index, th, tw, mode, ci, cj, flip, 0}: the stored sample
