@@ -23,6 +23,7 @@ File contract (state_dicts, read with strict=True by imdb.load_pretrained and af
   affect_mm_gru(1 / 0)     lf_gru.pt / ef_gru.pt                               --fusion 0 | 1 are not wired yet)
   imdb_mm_lrtf()           best_lrtf.pt                                       (builders: --fuse 2 / --fusion 5 are not wired
   affect_mm_lrtf()         lrtf.pt                                             yet)
+  imdb_mm_mim()            best_mim.pt                                        (builder: --fuse 3 is not wired yet)
 The b1_ / b2_ copies are the names affect_dyn.py:211 (`--model v2`) reads, which a reference user makes by renaming.
 """
 import copy
@@ -87,6 +88,12 @@ def imdb_mm_lrtf(rank=128):
     """imdb_mm.py `--fuse 2` (lrtf: two MaxOut_MLPs, LowRankTensorFusion([512, 512], 512, 128), Linear(512, 23); best_lrtf.pt
     through imdb_mm.file_name(dir, 2)) and its learning rate."""
     return _tag_maxout(I.low_rank_fusion_maxout(rank)), 8e-3
+
+
+def imdb_mm_mim(output_dim=1024):
+    """imdb_mm.py `--fuse 3` (mim: two MaxOut_MLPs, MultiplicativeInteractions2Modal([512, 512], 1024, 'matrix'),
+    Linear(1024, 23); best_mim.pt through imdb_mm.file_name(dir, 3)) and its learning rate."""
+    return _tag_maxout(I.multiplicative_fusion_maxout(output_dim)), 8e-3
 
 
 def affect_uni(mod, enc='transformer', hidden_dim1=0, hidden_dim2=0, clf=False):

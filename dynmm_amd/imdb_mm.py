@@ -6,7 +6,9 @@ F1-macro), save it under --log-dir and test it with single_test (F1 micro / macr
   --fuse 1 (lf): MaxOut_MLP(512, 512, 300, linear_layer=False), MaxOut_MLP(512, 1024, 4096, 512, False), Concat,
                  Linear(1024, 23), lr 8e-3 -> best_lf.pt (DynMMNet's branch3)
   --fuse 0 (ef, the reference's default): identity encoders, Concat, MaxOut_MLP(23, 512, 4396), lr 4e-2 -> best_ef.pt
---fuse 2 / 3 (LowRankTensorFusion, MultiplicativeInteractions2Modal) are refused.  Data as dynmm_amd.imdb."""
+--fuse 2 / 3 (LowRankTensorFusion, MultiplicativeInteractions2Modal) are refused from the command line; both models run on
+the HIP path through their builders, experts.imdb_mm_lrtf() -> best_lrtf.pt and experts.imdb_mm_mim() -> best_mim.pt (lr 8e-3,
+trained with experts.train like the others).  Data as dynmm_amd.imdb."""
 import argparse
 import os
 

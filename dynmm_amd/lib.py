@@ -197,6 +197,10 @@ SIGNATURES = {
     'dynmm_lrtf_fwd': (c_i, [_PP, _PP, _IP, c_i, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_f]),
     'dynmm_lrtf_bwd_workspace_bytes': (c_sz, [c_i, _IP, c_i, c_i, c_i]),
     'dynmm_lrtf_bwd': (c_i, [c_f, _PP, _PP, _IP, c_i, c_f, _PP, _PP, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_f]),
+    'dynmm_mim_fwd_workspace_bytes': (c_sz, [c_i] * 4),
+    'dynmm_mim_fwd': (c_i, [c_f] * 8 + [c_sz] + [c_i] * 4 + [c_f]),
+    'dynmm_mim_bwd_workspace_bytes': (c_sz, [c_i] * 4),
+    'dynmm_mim_bwd': (c_i, [c_f] * 13 + [c_sz] + [c_i] * 4 + [c_f]),
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 

@@ -15,6 +15,17 @@ nor pinned to a commit (imdb_dyn.py:10-13).  The modules below restate MultiBenc
                                   hid2val = Linear(second_hidden, num_outputs) or None (linear_layer=False)
   Concat                          cat([m.flatten(1)], 1)
   LowRankTensorFusion             nn.affect.LowRankTensorFusion (one class for both data sets)
+  MultiplicativeInteractions2Modal(input_dims=[n, m], output_dim=D, output='matrix', flatten=False, clip=None,
+                                   grad_clip=None, flip=False)
+                                  parameters (state_dict keys, in this order) W [n, m, D], U [n, D], V [m, D]: xavier_normal_;
+                                  b [D]: normal_.  forward(modalities): m1, m2 = modalities (swapped under flip, each
+                                  flattened to [B, -1] under flatten);
+                                    Wprime = einsum('bn,nmd->bmd', m1, W) + V        # [B, m, D]
+                                    bprime = m1 @ U + b
+                                    out    = einsum('bm,bmd->bd', m2, Wprime) + bprime
+                                  that is out[b,d] = sum_{n,m} m1[b,n] m2[b,m] W[n,m,d] + (m2 V)[b,d] + (m1 U)[b,d] + b[d]; one
+                                  operator here (ops_mlp.mim, csrc/mim.hip), which never writes Wprime.  The other outputs
+                                  ('vector', 'scalar'), clip and grad_clip are not built by the reference and are refused.
   MMDL(encoders, fusion, head)    head(fusion([enc_i(x_i)]))   (has_padding=False)
 
 and, from the reference's own file, DynMMNet (imdb_dyn.py:29-114): expert 1 = text MLP encoder + MLP head, expert 2 =
@@ -111,6 +122,39 @@ class Concat(nn.Module):
         return torch.cat([m.flatten(1) for m in modalities], dim=1)
 
 
+class MultiplicativeInteractions2Modal(nn.Module):
+    """fusions.common_fusions.MultiplicativeInteractions2Modal with output='matrix' (the module docstring holds the
+    definition) on ops_mlp.mim."""
+
+    def __init__(self, input_dims, output_dim, output, flatten=False, clip=None, grad_clip=None, flip=False):
+        super().__init__()
+        if len(input_dims) != 2:
+            raise NotImplementedError(f'MultiplicativeInteractions2Modal takes two modalities, got input_dims {input_dims}')
+        if output != 'matrix':
+            raise NotImplementedError(f"MultiplicativeInteractions2Modal(output={output!r}): only 'matrix' has HIP kernels")
+        if clip is not None or grad_clip is not None:
+            raise NotImplementedError('MultiplicativeInteractions2Modal: clip / grad_clip are not built on the HIP path')
+        self.input_dims, self.output_dim, self.output = list(input_dims), output_dim, output
+        self.flatten, self.clip, self.grad_clip, self.flip = flatten, clip, grad_clip, flip
+        n, m = self.input_dims
+        self.W = nn.Parameter(torch.empty(n, m, output_dim))
+        nn.init.xavier_normal_(self.W)
+        self.U = nn.Parameter(torch.empty(n, output_dim))
+        nn.init.xavier_normal_(self.U)
+        self.V = nn.Parameter(torch.empty(m, output_dim))
+        nn.init.xavier_normal_(self.V)
+        self.b = nn.Parameter(torch.empty(output_dim))
+        nn.init.normal_(self.b)
+
+    def forward(self, modalities):
+        if len(modalities) != 2:
+            raise ValueError(f'MultiplicativeInteractions2Modal takes two modalities, got {len(modalities)}')
+        m1, m2 = (modalities[1], modalities[0]) if self.flip else (modalities[0], modalities[1])
+        if self.flatten:
+            m1, m2 = torch.flatten(m1, start_dim=1), torch.flatten(m2, start_dim=1)
+        return M.mim(m1, m2, self.W, self.U, self.V, self.b)
+
+
 class MMDL(nn.Module):
     """Supervised_Learning.MMDL with has_padding=False and tensor-valued encoders; the encoders run side by side."""
 
@@ -138,6 +182,12 @@ def low_rank_fusion_maxout(rank=128):
     """imdb_mm.py:43-47 (`--fuse 2`, saved as best_lrtf.pt)."""
     return MMDL([MaxOut_MLP(512, 512, 300, linear_layer=False), MaxOut_MLP(512, 1024, 4096, 512, False)],
                 LowRankTensorFusion([512, 512], 512, rank), Linear(512, NUM_CLASSES))
+
+
+def multiplicative_fusion_maxout(output_dim=1024):
+    """imdb_mm.py:49-53 (`--fuse 3`, saved as best_mim.pt)."""
+    return MMDL([MaxOut_MLP(512, 512, 300, linear_layer=False), MaxOut_MLP(512, 1024, 4096, 512, False)],
+                MultiplicativeInteractions2Modal([512, 512], output_dim, 'matrix'), Linear(output_dim, NUM_CLASSES))
 
 
 class DynMMNet(nn.Module):

@@ -2,8 +2,9 @@
 
 Activations are [B, D] fp32 rows; every Linear is `ops_seq.linear_bdt` (the 1x1 MFMA convolution).  The kernels added for
 this path live in csrc/mlp.hip: MultiBench's Maxout -> BatchNorm1d -> Dropout fused (and the plain BatchNorm1d of a
-MaxOut_MLP's input), the multilabel mixture head, the evaluation counts and the hard-gate partition.  As everywhere in
-dynmm_amd there is no CPU / eager fallback.
+MaxOut_MLP's input), the multilabel mixture head, the evaluation counts and the hard-gate partition.  The multiplicative
+interactions fusion of imdb_mm.py `--fuse 3` (`mim`) runs on csrc/mim.hip.  As everywhere in dynmm_amd there is no CPU / eager
+fallback.
 """
 import ctypes as C
 
@@ -87,6 +88,84 @@ def maxout_bn(z, bn, drop=None, maxout=True):
     if drop is not None and drop[0] > 0 and (bn.training or not bn.track_running_stats):
         d = S.Drop(drop[0], drop[1], drop[2], (B, M), z.device)
     return _MaxoutBN.apply(z, bn.weight, bn.bias, bn, bool(maxout), d)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# multiplicative interactions fusion (MultiBench fusions.common_fusions.MultiplicativeInteractions2Modal), csrc/mim.hip
+# ---------------------------------------------------------------------------------------------------------------
+def _mim_operand(t, name, shape=None):
+    """a device, float32, contiguous operand (refused otherwise: the gradients are written in the operands' own layout)"""
+    if not torch.is_tensor(t):
+        raise L.DynmmHipError(f'mim: {name} must be a tensor, got {type(t).__name__}')
+    _chk(t, name)
+    if not t.is_contiguous():
+        raise L.DynmmHipError(f'mim: {name} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}')
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise L.DynmmHipError(f'mim: {name} must be {tuple(shape)}, got {tuple(t.shape)}')
+    return t
+
+
+class _MIM(Function):
+    """out [B, D] of (m1, m2, W, U, V, b).  Saves its inputs only."""
+
+    @staticmethod
+    def forward(ctx, m1, m2, W, U, V, b):
+        lib = _lib()
+        (B, N), (M, D) = m1.shape, V.shape
+        out = torch.empty((B, D), device=m1.device, dtype=torch.float32)
+        nb = lib.dynmm_mim_fwd_workspace_bytes(B, N, M, D)
+        ws = torch.empty(nb // 4, device=out.device, dtype=torch.float32)
+        L.check(lib.dynmm_mim_fwd(_p(m1), _p(m2), _p(W), _p(U), _p(V), _p(b), _p(out), _p(ws), nb, B, N, M, D, _stream()),
+                'mim_fwd')
+        ctx.save_for_backward(m1, m2, W, U, V)
+        ctx.params = (W, U, V, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib()
+        m1, m2, W, U, V = ctx.saved_tensors
+        g = _chk(g, 'grad')
+        (B, N), (M, D) = m1.shape, V.shape
+        need = ctx.needs_input_grad
+        need_p = any(need[2:])
+        if not (need_p or need[0] or need[1]):
+            return (None,) * 6
+        dm1 = torch.empty_like(m1) if need[0] else None
+        dm2 = torch.empty_like(m2) if need[1] else None
+        dst = [None] * 4
+        ret = [None] * 4
+        if need_p:
+            # the weight pass produces the four parameter gradients together: each lands in its parameter's slice of the flat
+            # gradient buffer (or in a fresh tensor under plain autograd)
+            for k, prm in enumerate(ctx.params):
+                dst[k], ret[k] = _grad_dst(prm)
+        nb, ws = 0, None
+        if need[0] or need[1]:
+            nb = lib.dynmm_mim_bwd_workspace_bytes(B, N, M, D)
+            ws = torch.empty(nb // 4, device=g.device, dtype=torch.float32)
+        L.check(lib.dynmm_mim_bwd(_p(g), _p(m1), _p(m2), _p(W), _p(U), _p(V), _p(dm1), _p(dm2), _p(dst[0]), _p(dst[1]),
+                                  _p(dst[2]), _p(dst[3]), _p(ws), nb, B, N, M, D, _stream()), 'mim_bwd')
+        _grads_enqueued()
+        ret = [t if n else None for t, n in zip(ret, need[2:])]
+        return (dm1, dm2, *ret)
+
+
+def mim(m1, m2, W, U, V, b):
+    """MultiBench's MultiplicativeInteractions2Modal(output='matrix') on m1 [B, n], m2 [B, m]:
+    out = einsum('bm,bmd->bd', m2, einsum('bn,nmd->bmd', m1, W) + V) + m1 @ U + b -> [B, D], with W [n, m, D], U [n, D],
+    V [m, D], b [D].  One operator forward and backward (csrc/mim.hip); no [B, m, D] tensor exists."""
+    m1, m2 = _mim_operand(m1, 'm1'), _mim_operand(m2, 'm2')
+    if m1.dim() != 2 or m2.dim() != 2 or m1.shape[0] != m2.shape[0]:
+        raise L.DynmmHipError(f'mim: m1 [B, n] and m2 [B, m] must share B, got {tuple(m1.shape)} and {tuple(m2.shape)}')
+    if not torch.is_tensor(W) or W.dim() != 3:
+        raise L.DynmmHipError(f'mim: W must be [n, m, D], got {tuple(W.shape) if torch.is_tensor(W) else type(W).__name__}')
+    n, m, D = m1.shape[1], m2.shape[1], W.shape[2]
+    W = _mim_operand(W, 'W', (n, m, D))
+    U, V, b = _mim_operand(U, 'U', (n, D)), _mim_operand(V, 'V', (m, D)), _mim_operand(b, 'b', (D,))
+    if 0 in (m1.shape[0], n, m, D):
+        raise L.DynmmHipError(f'mim: empty operands (B, n, m, D) = {(m1.shape[0], n, m, D)}')
+    return _MIM.apply(m1, m2, W, U, V, b)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -759,6 +759,23 @@ int dynmm_lrtf_bwd(const float* g, const float* const* zs, const float* const* f
                    float* const* dzs, float* const* dfs, float* dw, float* dbias, float* workspace, size_t workspace_bytes,
                    int B, int O, int R, void* stream);
 
+/* ---- multiplicative interactions fusion (MultiBench fusions.common_fusions.MultiplicativeInteractions2Modal, output='matrix':
+ * imdb_mm.py --fuse 3), csrc/mim.hip ----
+ *   out[b,d] = sum_{n,m} m1[b,n] m2[b,m] W[n,m,d] + sum_m m2[b,m] V[m,d] + sum_n m1[b,n] U[n,d] + bias[d]
+ * m1 [B, N], m2 [B, M], W [N, M, D], U [N, D], V [M, D], bias [D], out [B, D]; all fp32, contiguous; any B, N, M, D >= 1 (W may
+ * hold more than 2^31 elements: it is indexed in 64 bits).  Nothing of shape [B, M, D] or [B, N M] is written, forward or
+ * backward.  fwd: the n range is split over workgroups; the workspace holds the U / V / bias term and the partial outputs, summed
+ * in a fixed order.  bwd: g = the gradient of out.  dW with dU, dV and dbias: the parameter gradients, all of them or (dW NULL)
+ * none.  dm1 / dm2 may each be NULL; with both NULL the pass over W for the inputs is skipped and no workspace is needed.
+ * Gradients are OVERWRITTEN.  No floating-point atomics: equal inputs give equal bits. */
+size_t dynmm_mim_fwd_workspace_bytes(int B, int N, int M, int D);
+int dynmm_mim_fwd(const float* m1, const float* m2, const float* W, const float* U, const float* V, const float* bias, float* out,
+                  float* workspace, size_t workspace_bytes, int B, int N, int M, int D, void* stream);
+size_t dynmm_mim_bwd_workspace_bytes(int B, int N, int M, int D);
+int dynmm_mim_bwd(const float* g, const float* m1, const float* m2, const float* W, const float* U, const float* V, float* dm1,
+                  float* dm2, float* dW, float* dU, float* dV, float* dbias, float* workspace, size_t workspace_bytes, int B,
+                  int N, int M, int D, void* stream);
+
 /* ---- NYUv2 input pipeline (FusionDynMM/src/preprocessing.py), csrc/rgbd_aug.hip ---- */
 /* One batch of network inputs from decoded samples kept on the device: rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit,
  * label [S,H0,W0] uint8.  params [N,8] int32 per output sample: {stored index, th, tw, mode, ci, cj, flip, 0}: the stored sample
