@@ -4,8 +4,10 @@ Counterpart of ModalityDynMM/affect/affect_mm.py (Step I): train the late-fusion
 Transformer(35, 60), Transformer(74, 120), Transformer(300, 120), Concat, MLP(300, 128, 1)) with Supervised_Learning.train
 (AdamW lr 1e-4, weight decay 1e-4, L1Loss, clip_grad_norm_(8), early stopping on the validation loss), save it as
 lf_tran.pt and b2_lf_tran.pt (the name dynmm_amd.affect --model v2 reads) under --log-dir, reload it and test it on the
-validation and the test split with single_test (Accuracy, Loss, Corr).  The GRU fusions (--fusion 0, 1, 5), MULT (4) and
-the early-fusion transformer (2) are refused.  Data as dynmm_amd.affect."""
+validation and the test split with single_test (Accuracy, Loss, Corr).  The other switches are refused: the GRU fusions
+(--fusion 0, 1, 5) and the early-fusion transformer (--fusion 2, ef_tran: Transformer(409, 300) + MLP(300, 128, 1)) run on the
+HIP path at the module level (experts.affect_mm_gru, affect_mm_lrtf, affect_mm_ef_tran; file_names gives their file names) but
+are not wired to the command line yet; MULT (--fusion 4) has no HIP kernels.  Data as dynmm_amd.affect."""
 import argparse
 import os
 

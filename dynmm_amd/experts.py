@@ -24,6 +24,7 @@ File contract (state_dicts, read with strict=True by imdb.load_pretrained and af
   imdb_mm_lrtf()           best_lrtf.pt                                       (builders: --fuse 2 / --fusion 5 are not wired
   affect_mm_lrtf()         lrtf.pt                                             yet)
   imdb_mm_mim()            best_mim.pt                                        (builder: --fuse 3 is not wired yet)
+  affect_mm_ef_tran()      ef_tran.pt                                         (builder: --fusion 2 is not wired yet)
 The b1_ / b2_ copies are the names affect_dyn.py:211 (`--model v2`) reads, which a reference user makes by renaming.
 """
 import copy
@@ -114,7 +115,9 @@ def affect_uni(mod, enc='transformer', hidden_dim1=0, hidden_dim2=0, clf=False):
 
 
 def affect_mm(fusion):
-    """affect_mm.py: the MMDL of `--fusion` (3: late-fusion transformers, DynMMNetV2's branch2)."""
+    """affect_mm.py: the MMDL of `--fusion` (3: late-fusion transformers, DynMMNetV2's branch2).  The other switches are refused;
+    the models of 0 / 1 (affect_mm_gru), 2 (affect_mm_ef_tran) and 5 (affect_mm_lrtf) are built by their own functions, 4 (MULT)
+    has no HIP kernels."""
     if fusion == 3:
         return A.late_fusion_transformer()
     if fusion in (0, 1):
@@ -127,8 +130,9 @@ def affect_mm(fusion):
     if fusion == 4:
         raise NotImplementedError('affect_mm --fusion 4 (mult): MULTModel has no HIP kernels')
     if fusion == 2:
-        raise NotImplementedError('affect_mm --fusion 2 (ef_tran): the early-fusion Transformer(409, 300) head is not built '
-                                  'on the HIP path')
+        raise NotImplementedError('affect_mm --fusion 2 (ef_tran): the driver switch is not wired yet; the early-fusion '
+                                  'Transformer(409, 300) model itself runs on the HIP path: '
+                                  'dynmm_amd.nn.affect.early_fusion_transformer, experts.affect_mm_ef_tran')
     raise ValueError(f'--fusion {fusion}: one of 0-5')
 
 
@@ -162,6 +166,12 @@ def affect_mm_lrtf(rank=32):
     """affect_mm.py `--fusion 5` (lrtf: three GRUWithLinear encoders, LowRankTensorFusion([32, 32, 128], 128, 32),
     MLP(128, 512, 1); lrtf.pt through affect_mm.file_names(dir, 5))."""
     return A.low_rank_fusion_gru(rank)
+
+
+def affect_mm_ef_tran():
+    """affect_mm.py `--fusion 2` (ef_tran: Identity encoders, ConcatEarly, Sequential(Transformer(409, 300), MLP(300, 128, 1));
+    ef_tran.pt through affect_mm.file_names(dir, 2)).  nhead = 5 at d_model = 300 is head dimension 60: ops_seq.mha_wide."""
+    return A.early_fusion_transformer()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -201,6 +201,9 @@ SIGNATURES = {
     'dynmm_mim_fwd': (c_i, [c_f] * 8 + [c_sz] + [c_i] * 4 + [c_f]),
     'dynmm_mim_bwd_workspace_bytes': (c_sz, [c_i] * 4),
     'dynmm_mim_bwd': (c_i, [c_f] * 13 + [c_sz] + [c_i] * 4 + [c_f]),
+    'dynmm_attn_supported': (c_i, [c_i, c_i, c_i]),
+    'dynmm_attn_fwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, _DP, c_f]),
+    'dynmm_attn_bwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, _DP, c_f]),
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 

@@ -117,7 +117,7 @@ def encoder_layer(h, layer, heads):
     # the link and in_proj's input-gradient epilogue adds it (no accumulation pass by autograd)
     link = ops.GradLink() if LINK_RESIDUAL else None
     qkv = S.linear_bdt(h, sa.in_proj_weight, sa.in_proj_bias, link=link)
-    a = S.mha_core(qkv, heads, drop=(p_att, site, 'attn'))
+    a = S.attention(qkv, heads, drop=(p_att, site, 'attn'))      # dh <= 32: mha_core, above: mha_wide
     o = S.linear_bdt(a, sa.out_proj.weight, sa.out_proj.bias)
     h1 = S.layernorm_bdt(o, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps, residual=h, drop=(p1, site + 1, 'dropout1'),
                          res_link=link)
@@ -322,6 +322,13 @@ def early_fusion_gru():
     """affect_mm.py:40-44 (`--fusion 0`, saved as ef_gru.pt)."""
     return MMDL([Identity(), Identity(), Identity()], ConcatEarly(),
                 Sequential(GRU(409, 512, dropout=True, has_padding=True), MLP(512, 256, 1)))
+
+
+def early_fusion_transformer():
+    """affect_mm.py:56-59 (`--fusion 2`, saved as ef_tran.pt): one transformer over the three modalities side by side.
+    d_model = 300 at nhead = 5 is head dimension 60: the attention core is ops_seq.mha_wide (csrc/attn.hip), the feed-forward
+    block runs layer by layer (the fused block serves D <= 128)."""
+    return MMDL([Identity(), Identity(), Identity()], ConcatEarly(), Sequential(Transformer(409, 300), MLP(300, 128, 1)))
 
 
 def late_fusion_transformer():

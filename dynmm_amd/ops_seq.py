@@ -2,7 +2,7 @@
 
 Activations are [B, D, T] fp32 (the layout the reference feeds its Conv1d after `x.permute([0, 2, 1])`); every Linear
 / Conv1d(k=1) is `linear_bdt` = the implicit-GEMM MFMA convolution of ops.conv2d with H = 1, W = T.  The kernels
-added for this path live in csrc/seq.hip.  As everywhere in dynmm_amd there is no CPU / eager fallback.
+added for this path live in csrc/seq.hip (attention for head dimensions above 32: csrc/attn.hip).  As everywhere in dynmm_amd there is no CPU / eager fallback.
 """
 import ctypes as C
 import itertools
@@ -520,6 +520,53 @@ def mha_core(qkv, heads, drop=None):
     B, D3, T = qkv.shape
     d = Drop(drop[0], drop[1], drop[2], (B * heads, T, T), qkv.device) if drop is not None and drop[0] > 0 else None
     return _MHACore.apply(qkv, heads, d)
+
+
+MHA_CORE_MAX_DH = 32     # csrc/seq.hip: kSeqMaxDh
+
+
+class _MHAWide(Function):
+    """_MHACore's contract on the matrix-core kernels of csrc/attn.hip (head dimensions up to 64)."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, drop=None):
+        lib = _lib()
+        qkv = _chk(qkv, 'qkv')
+        B, D3, T = qkv.shape
+        D = D3 // 3
+        out = torch.empty((B, D, T), device=qkv.device, dtype=torch.float32)
+        probs = torch.empty((B * heads, T, T), device=qkv.device, dtype=torch.float32)
+        L.check(lib.dynmm_attn_fwd(_p(qkv), _p(out), _p(probs), B, D, T, heads, _drop_arg(drop), _stream()), 'attn_fwd')
+        ctx.drop = drop
+        ctx.save_for_backward(qkv, probs)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib()
+        qkv, probs = ctx.saved_tensors
+        g = _chk(g, 'grad')
+        B, D3, T = qkv.shape
+        dqkv = torch.empty_like(qkv)
+        L.check(lib.dynmm_attn_bwd(_p(g), _p(qkv), _p(probs), _p(dqkv), B, D3 // 3, T, ctx.heads, _drop_arg(ctx.drop),
+                                   _stream()), 'attn_bwd')
+        return dqkv, None, None
+
+
+def mha_wide(qkv, heads, drop=None):
+    """mha_core for head dimensions up to 64 (T <= 64): the same function, arguments and dropout site (name, shape
+    (B*heads, T, T), indexing, generator decisions) on 16x16 fp32 matrix-core tiles (csrc/attn.hip)."""
+    B, D3, T = qkv.shape
+    d = Drop(drop[0], drop[1], drop[2], (B * heads, T, T), qkv.device) if drop is not None and drop[0] > 0 else None
+    return _MHAWide.apply(qkv, heads, d)
+
+
+def attention(qkv, heads, drop=None):
+    """The attention core of an encoder layer: mha_core up to head dimension 32 (every model with d_model <= 160 at nhead = 5:
+    the kernel and the launch they always had), mha_wide above it (Transformer(409, 300): dh = 60)."""
+    dh = qkv.shape[1] // 3 // heads
+    return mha_core(qkv, heads, drop) if dh <= MHA_CORE_MAX_DH else mha_wide(qkv, heads, drop)
 
 
 class _MoEBlend(Function):

@@ -776,6 +776,22 @@ int dynmm_mim_bwd(const float* g, const float* m1, const float* m2, const float*
                   float* dm2, float* dW, float* dU, float* dV, float* dbias, float* workspace, size_t workspace_bytes, int B,
                   int N, int M, int D, void* stream);
 
+/* ---- self-attention for head dimensions up to 64 (nn.TransformerEncoderLayer(d_model = 300, nhead = 5) of affect_mm.py
+ * --fusion 2: dh = 60), csrc/attn.hip ----
+ * The tensors and the function of dynmm_mha_drop_fwd / _bwd (qkv [B, 3D, T] split q | k | v, out [B, D, T], probs
+ * [B*heads, T, T] BEFORE dropout with rows that sum to 1, dqkv [B, 3D, T]; q is scaled by 1/sqrt(dh) before the product), on
+ * 16x16 tiles of the fp32 matrix cores (v_mfma_f32_16x16x4_f32: fp32 in, fp32 accumulate, exact).  1 <= D/heads <= 64 and
+ * 1 <= T <= 64, any B and heads (dynmm_attn_supported = 1); outside that DYNMM_EUNSUPPORTED, a malformed call DYNMM_EINVAL,
+ * nothing written in either case.  One workgroup per (sample, head), no atomics, no workspace, no host synchronisation: equal
+ * inputs give equal bits, and both calls can be captured.  drop (optional): the dropout site of the probabilities, indexed as
+ * dynmm_mha_drop_fwd indexes it — injected flags are the flat [B*heads, T, T] bytes, and the generator draws the decisions
+ * dynmm_mha_drop_fwd draws for the same seed, offset and step. */
+int dynmm_attn_supported(int D, int T, int heads);
+int dynmm_attn_fwd(const float* qkv, float* out, float* probs, int B, int D, int T, int heads, const dynmm_dropout* drop,
+                   void* stream);
+int dynmm_attn_bwd(const float* g, const float* qkv, const float* probs, float* dqkv, int B, int D, int T, int heads,
+                   const dynmm_dropout* drop, void* stream);
+
 /* ---- NYUv2 input pipeline (FusionDynMM/src/preprocessing.py), csrc/rgbd_aug.hip ---- */
 /* One batch of network inputs from decoded samples kept on the device: rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit,
  * label [S,H0,W0] uint8.  params [N,8] int32 per output sample: {stored index, th, tw, mode, ci, cj, flip, 0}: the stored sample
