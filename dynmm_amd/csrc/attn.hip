@@ -30,14 +30,12 @@
 // with one lane read per tile.
 #include "common.h"
 #include "dropout.h"
+#include "mfma.h"
 
 namespace dynmm {
 
 constexpr int kAttnMaxT = 64;
 constexpr int kAttnMaxDh = 64;
-
-typedef float attn_f4 __attribute__((ext_vector_type(4)));
-#define ATTN_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // Staging of rows 16 w .. 16 w + 15 of a token-major tile [.][DH + 4] from src [channel][T]: wave w's lanes take token
 // 16 w + (lane & 15), channels 4 s + (lane >> 4).  attn_load issues the DH / 4 loads of a lane (clamped addresses, nothing depends
@@ -124,15 +122,15 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
     const unsigned bits = dropping ? attn_draw(drop, row, T, g) : 0u;
 
     // S^T[j][i] = sum_c K[j][c] Q[i][c]: four key tiles side by side (independent accumulators cover the 40-cycle latency)
-    attn_f4 s[4];
+    f32x4 s[4];
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt) s[jt] = attn_f4{0.f, 0.f, 0.f, 0.f};
+    for (int jt = 0; jt < 4; ++jt) s[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
         const float qv = qs[i * LD + 4 * k + g];
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt)
-            if (jt < nt) s[jt] = ATTN_MFMA(ks[(16 * jt + li) * LD + 4 * k + g], qv, s[jt]);
+            if (jt < nt) s[jt] = mfma_16x16x4(ks[(16 * jt + li) * LD + 4 * k + g], qv, s[jt]);
     }
     float mx = -INFINITY;
 #pragma unroll
@@ -165,9 +163,9 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
         }
     }
     // out^T[c][i] = sum_j V[j][c] P'[i][j]: k-step (jt, r) = keys 16 jt + 4 g + r, P' straight from the accumulators
-    attn_f4 o[CT];
+    f32x4 o[CT];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) o[ct] = attn_f4{0.f, 0.f, 0.f, 0.f};
+    for (int ct = 0; ct < CT; ++ct) o[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt)
         if (jt < nt) {
@@ -175,7 +173,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
             for (int r = 0; r < 4; ++r) {
                 const float* vr = vs + (16 * jt + 4 * g + r) * LD + li;
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) o[ct] = ATTN_MFMA(vr[16 * ct], s[jt][r], o[ct]);
+                for (int ct = 0; ct < CT; ++ct) o[ct] = mfma_16x16x4(vr[16 * ct], s[jt][r], o[ct]);
             }
         }
     float* ob = out + ((size_t)b * D + (size_t)h * dh) * T;
@@ -228,7 +226,7 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
         const bool dropping = drop.p > 0.f;
         const unsigned bits = dropping ? attn_draw(drop, row, T, g) : 0u;
         // P of this lane's query, keys 16 jt + 4 g + r (clamped addresses, zeros outside T x T)
-        attn_f4 p[4], pk[4], d[4];
+        f32x4 p[4], pk[4], d[4];
         const float* pg = probs + row * T;
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt)
@@ -239,13 +237,13 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
             }
         // dP'^T[j][i] = sum_c V[j][c] dOut[i][c]
 #pragma unroll
-        for (int jt = 0; jt < 4; ++jt) d[jt] = attn_f4{0.f, 0.f, 0.f, 0.f};
+        for (int jt = 0; jt < 4; ++jt) d[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < KS; ++k) {
             const float gv = gs[i * LD + 4 * k + g];
 #pragma unroll
             for (int jt = 0; jt < 4; ++jt)
-                if (jt < nt) d[jt] = ATTN_MFMA(vs[(16 * jt + li) * LD + 4 * k + g], gv, d[jt]);
+                if (jt < nt) d[jt] = mfma_16x16x4(vs[(16 * jt + li) * LD + 4 * k + g], gv, d[jt]);
         }
         // dP = dP' * keep / (1 - p);  P' = P * keep / (1 - p);  dS = P (dP - sum_j P dP)
         float dot = 0.f;
@@ -271,9 +269,9 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
                 pps[o] = pk[jt][r];
             }
         // dQ^T[c][i] = scale sum_j K[j][c] dS[i][j]: dS straight from the registers
-        attn_f4 a[CT];
+        f32x4 a[CT];
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) a[ct] = attn_f4{0.f, 0.f, 0.f, 0.f};
+        for (int ct = 0; ct < CT; ++ct) a[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt)
             if (jt < nt) {
@@ -281,7 +279,7 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
                 for (int r = 0; r < 4; ++r) {
                     const float* kr = ks + (16 * jt + 4 * g + r) * LD + li;
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) a[ct] = ATTN_MFMA(kr[16 * ct], d[jt][r], a[ct]);
+                    for (int ct = 0; ct < CT; ++ct) a[ct] = mfma_16x16x4(kr[16 * ct], d[jt][r], a[ct]);
                 }
             }
         float* dq = dqkv + ((size_t)b * 3 * D + (size_t)h * dh) * T;
@@ -296,9 +294,9 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
     __syncthreads();
     if (!live) return;
     // wave w now owns KEYS 16 w + li:  dK^T[c][j] = scale sum_i Q[i][c] dS[i][j],  dV^T[c][j] = sum_i dOut[i][c] P'[i][j]
-    attn_f4 ak[CT], av[CT];
+    f32x4 ak[CT], av[CT];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) ak[ct] = av[ct] = attn_f4{0.f, 0.f, 0.f, 0.f};
+    for (int ct = 0; ct < CT; ++ct) ak[ct] = av[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int it = 0; it < nt; ++it) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -308,8 +306,8 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
             const float* gr = gs + q * LD + li;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-                ak[ct] = ATTN_MFMA(qr[16 * ct], dsv, ak[ct]);
-                av[ct] = ATTN_MFMA(gr[16 * ct], ppv, av[ct]);
+                ak[ct] = mfma_16x16x4(qr[16 * ct], dsv, ak[ct]);
+                av[ct] = mfma_16x16x4(gr[16 * ct], ppv, av[ct]);
             }
         }
     }
@@ -332,15 +330,6 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
 using namespace dynmm;
 
 #define ST ((hipStream_t)stream)
-
-static DropSpec attn_drop_spec(const dynmm_dropout* d) {
-    DropSpec s{};
-    if (d && d->p > 0.f) {
-        s.mask = d->mask; s.step = d->step; s.seed = d->seed; s.offset = d->offset; s.p = d->p;
-    }
-    return s;
-}
-static bool attn_drop_ok(const dynmm_dropout* d) { return !d || (d->p >= 0.f && d->p < 1.f); }
 
 template <int DH, bool BWD>
 static int launch_attn(const float* g, const float* qkv, float* out_or_dqkv, float* probs, int B, int D, int T, int heads,
@@ -369,17 +358,17 @@ extern "C" int dynmm_attn_supported(int D, int T, int heads) {
 extern "C" int dynmm_attn_fwd(const float* qkv, float* out, float* probs, int B, int D, int T, int heads,
                               const dynmm_dropout* drop, void* stream) {
     (void)hipGetLastError();
-    if (!qkv || !out || !probs || B <= 0 || D <= 0 || T <= 0 || heads <= 0 || D % heads != 0 || !attn_drop_ok(drop)) return DYNMM_EINVAL;
+    if (!qkv || !out || !probs || B <= 0 || D <= 0 || T <= 0 || heads <= 0 || D % heads != 0 || !drop_ok(drop)) return DYNMM_EINVAL;
     if (!dynmm_attn_supported(D, T, heads)) return DYNMM_EUNSUPPORTED;
-    if (D / heads <= 32) return launch_attn<32, false>(nullptr, qkv, out, probs, B, D, T, heads, attn_drop_spec(drop), ST);
-    return launch_attn<64, false>(nullptr, qkv, out, probs, B, D, T, heads, attn_drop_spec(drop), ST);
+    if (D / heads <= 32) return launch_attn<32, false>(nullptr, qkv, out, probs, B, D, T, heads, drop_spec(drop), ST);
+    return launch_attn<64, false>(nullptr, qkv, out, probs, B, D, T, heads, drop_spec(drop), ST);
 }
 
 extern "C" int dynmm_attn_bwd(const float* g, const float* qkv, const float* probs, float* dqkv, int B, int D, int T, int heads,
                               const dynmm_dropout* drop, void* stream) {
     (void)hipGetLastError();
-    if (!g || !qkv || !probs || !dqkv || B <= 0 || D <= 0 || T <= 0 || heads <= 0 || D % heads != 0 || !attn_drop_ok(drop)) return DYNMM_EINVAL;
+    if (!g || !qkv || !probs || !dqkv || B <= 0 || D <= 0 || T <= 0 || heads <= 0 || D % heads != 0 || !drop_ok(drop)) return DYNMM_EINVAL;
     if (!dynmm_attn_supported(D, T, heads)) return DYNMM_EUNSUPPORTED;
-    if (D / heads <= 32) return launch_attn<32, true>(g, qkv, dqkv, const_cast<float*>(probs), B, D, T, heads, attn_drop_spec(drop), ST);
-    return launch_attn<64, true>(g, qkv, dqkv, const_cast<float*>(probs), B, D, T, heads, attn_drop_spec(drop), ST);
+    if (D / heads <= 32) return launch_attn<32, true>(g, qkv, dqkv, const_cast<float*>(probs), B, D, T, heads, drop_spec(drop), ST);
+    return launch_attn<64, true>(g, qkv, dqkv, const_cast<float*>(probs), B, D, T, heads, drop_spec(drop), ST);
 }

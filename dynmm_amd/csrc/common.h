@@ -64,6 +64,7 @@ __device__ __forceinline__ T block_reduce_sum_256(T v, T* smem) {
 
 // Swish z * sigmoid(z) and Hswish z * relu6(z + 3) / 6 (model_utils.py:100-115), in the reference's order of operations.
 // (z -> -inf: expf(-z) = +inf, the quotient is -0: finite, no NaN.)
+__device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + expf(-v)); }
 __device__ __forceinline__ float swish_fwd(float v) { return v / (1.f + expf(-v)); }
 __device__ __forceinline__ float hswish_fwd(float v) { return v * fminf(fmaxf(v + 3.f, 0.f), 6.f) / 6.f; }
 

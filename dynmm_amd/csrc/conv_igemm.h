@@ -3,9 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mfma.h"
+
 namespace dynmm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct IgemmArgs {
     const float* x;        // gemm input  [N, Ci, H, W]  (first c_in_split channels)

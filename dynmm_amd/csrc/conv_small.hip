@@ -367,7 +367,6 @@ int launch_co8_wgrad(const float* x, const float* x2, const float* dy, float* dw
 // A workgroup owns 64 channels x (4 rows x 64 cols) of one image: wave w = channel tile w & 1, output rows
 // 2 * (w >> 1) + {0, 1}, i.e. 1 channel tile x 4 pixel tiles of accumulators; its weight operand (84 / 28 values per
 // lane) lives in registers for the lifetime of the persistent workgroup.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // STATS (round 5): the stem convolution feeds a training-mode BatchNorm (resnet.py:229-231): a lane keeps running sums of y and
 // y^2 of the values it stores (8 channels: fp32 over its ~20 tiles x 2 rows x 4 columns), summed over the 16 lanes that share a

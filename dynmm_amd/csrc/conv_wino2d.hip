@@ -32,8 +32,6 @@
 
 namespace dynmm {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 struct Wino2dArgs {
     const float* x;         // [N, Ci, H, W] (input gradient: dy, Ci = the convolution's Co)
     const float* ut;        // [Ci][4][CoS][4]
@@ -152,7 +150,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino2d_kernel(const Wino2dArgs a)
     const int b_frag = kq * BCH + 2 * tl + 3;                            // + r * BROW
     const int zoff = 2 * tl + 3;
 
-    f32x4v acc[16][2];
+    f32x4 acc[16][2];
 #pragma unroll
     for (int tt = 0; tt < 16; ++tt)
 #pragma unroll

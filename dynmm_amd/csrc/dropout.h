@@ -1,5 +1,5 @@
-// Dropout with regenerated keep decisions (Philox sites), shared by the sequence kernels (seq.hip) and the
-// MaxOut_MLP kernels (mlp.hip).
+// Dropout with regenerated keep decisions (Philox sites), shared by the sequence kernels (seq.hip, seq_ffn.hip, attn.hip) and
+// the MaxOut_MLP kernels (mlp.hip); the one Philox-4x32-10 of the library (gate_se.hip draws its Gumbel noise from it too).
 #pragma once
 #include "common.h"
 
@@ -20,8 +20,18 @@ struct DropSpec {
     float p;
 };
 
-__device__ __forceinline__ void seq_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                  uint32_t k1, uint32_t out[4]) {
+// The kernels' DropSpec of an entry point's dynmm_dropout: all zero (no dropout) for none or p = 0.
+static inline DropSpec drop_spec(const dynmm_dropout* d) {
+    DropSpec s{};
+    if (d && d->p > 0.f) {
+        s.mask = d->mask; s.step = d->step; s.seed = d->seed; s.offset = d->offset; s.p = d->p;
+    }
+    return s;
+}
+static inline bool drop_ok(const dynmm_dropout* d) { return !d || (d->p >= 0.f && d->p < 1.f); }
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t out[4]) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
@@ -52,13 +62,13 @@ struct DropState {
         if (!(p > 0.f)) return 1.f;
         if (mask) return mask[idx] ? inv : 0.f;
         uint32_t r[4];
-        seq_philox4x32_10((uint32_t)idx, (uint32_t)((unsigned long long)idx >> 32), (uint32_t)off, (uint32_t)(off >> 32), k0, k1, r);
+        philox4x32_10((uint32_t)idx, (uint32_t)((unsigned long long)idx >> 32), (uint32_t)off, (uint32_t)(off >> 32), k0, k1, r);
         const float u = (float)(r[0] >> 8) * (1.f / 16777216.f);        // [0, 1)
         return u >= p ? inv : 0.f;
     }
     __device__ __forceinline__ void philox8(unsigned long long ctr, float k[8]) const {
         uint32_t r[4];
-        seq_philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)off, (uint32_t)(off >> 32), k0, k1, r);
+        philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)off, (uint32_t)(off >> 32), k0, k1, r);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             k[2 * q] = (r[q] & 0xffffu) >= thr16 ? inv : 0.f;

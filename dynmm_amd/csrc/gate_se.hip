@@ -4,6 +4,7 @@
 //     cumulative stage weights and the FLOP regulariser (single workgroup, latency-bound).
 // They are latency-bound, so each is ONE launch forward and ONE backward.
 #include "common.h"
+#include "dropout.h"
 
 namespace dynmm {
 
@@ -11,8 +12,6 @@ constexpr int kMaxC = 2048;     // ResNet-50 stage 4: 2048 channels
 constexpr int kMaxHid = 128;
 
 struct SeParams { const float* p[8]; };   // W1r b1r W2r b2r W1d b1d W2d b2d
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
 // one modality: s[C] (LDS) -> h[Hd] (LDS, also saved) -> g[C] (saved).  `act` = the hidden activation: ReLU saves the hidden
 // POST-activation (its backward tests h > 0), the smooth codes save the PRE-activation, which their derivative needs.
@@ -29,7 +28,7 @@ __device__ void se_mlp_fwd(const float* s, const float* W1, const float* b1, con
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         float acc = b2[c];
         for (int j = 0; j < Hd; ++j) acc += W2[c * Hd + j] * h_lds[j];
-        g_out[c] = sigmoidf_(acc);
+        g_out[c] = sigmoid_f(acc);
     }
     __syncthreads();
 }
@@ -376,19 +375,6 @@ __global__ void __launch_bounds__(256) gate_decide_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------
 constexpr int kAux = 6;   // aux[n] = {w, ysoft0, ysoft1, y1 (forward value), E0, E1}
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __device__ __forceinline__ float exp1_from_bits(uint32_t x) {
     const float u = ((float)(x >> 8) + 0.5f) * (1.f / 16777216.f);   // (0,1)
     return -logf(u);
@@ -426,7 +412,7 @@ __global__ void __launch_bounds__(256) reweigh_fwd_kernel(
     for (int c = threadIdx.x; c < C2; c += blockDim.x) acc += gn[c] * p_lds[c];   // same thread wrote gn[c]
     const float tot = block_reduce_sum_256<float>(acc, red);
     if (threadIdx.x == 0) {
-        const float w = sigmoidf_(tot / (float)C2);
+        const float w = sigmoid_f(tot / (float)C2);
         float e0, e1;
         if (noise) { e0 = noise[2 * n]; e1 = noise[2 * n + 1]; }
         else {

@@ -23,11 +23,10 @@
 // No workgroup ever waits for another one inside a kernel.  All loads are unconditional on clamped addresses, the value is
 // selected afterwards (batch tail, unit tail, length mask).
 #include "common.h"
+#include "mfma.h"
 
 namespace dynmm {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kArmResident = 1, kArmStepped = 2;
 constexpr int kResidentMaxHp = 512;
@@ -36,8 +35,6 @@ constexpr size_t kLdsBytes = 160 * 1024;
 constexpr int kStepThreads = 256;
 
 inline int gru_hp(int H) { return ceil_div(H, 16) * 16; }
-
-__device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + expf(-v)); }
 
 // packed[0 .. 3Hp^2): element (tile ut, k step kc, gate g, lane l) = W[g H + 16 ut + (l & 15)][4 kc + (l >> 4)];
 // packed[3Hp^2 ..):   the same of W^T per gate:                      W[g H + 4 kc + (l >> 4)][16 ut + (l & 15)].
@@ -64,9 +61,9 @@ __device__ __forceinline__ void tile_mma(const float* wt, const float* vec, int 
         const float w0 = wt[kc * 192], w1 = wt[kc * 192 + 64], w2 = wt[kc * 192 + 128];
         const int off = min(4 * kc + kq, kmax) * vstride + coloff;
         const float v0 = vec[off], v1 = vec[gstride + off], v2 = vec[2 * gstride + off];
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0, v0, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1, v1, a1, 0, 0, 0);
-        a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(w2, v2, a2, 0, 0, 0);
+        a0 = mfma_16x16x4(w0, v0, a0);
+        a1 = mfma_16x16x4(w1, v1, a1);
+        a2 = mfma_16x16x4(w2, v2, a2);
     }
 }
 

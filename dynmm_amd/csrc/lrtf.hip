@@ -24,11 +24,10 @@
 // dw[r] = sum g prod_m P_m: per-workgroup sums of the factor kernel, reduced over the output tiles in a fixed order.
 // All loads are unconditional on clamped addresses; the value is selected afterwards (sample, output and k tails).
 #include "common.h"
+#include "mfma.h"
 
 namespace dynmm {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxM = 3;
 constexpr int kThreads = 256;
@@ -50,8 +49,6 @@ struct Args {
 struct Ptrs {
     float* p[kMaxM];
 };
-
-#define LRTF_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // acc[m][i][j][reg] = P_m[r, b0 + 16 i + 4 (lane >> 4) + reg, o0 + 16 j + (lane & 15)] (rows / columns past B / O: clamped copies)
 template <int M>
@@ -78,10 +75,10 @@ __device__ __forceinline__ void p_tiles(const Args& a, int r, int b0, int o0, in
                 a1 = k < d ? a1 : 0.f;
                 const float* Fr = F + (size_t)(kcl + 1) * a.O;
                 const float v0 = Fr[oc0], v1 = Fr[oc1];
-                c00 = LRTF_MFMA(a0, v0, c00);
-                c01 = LRTF_MFMA(a0, v1, c01);
-                c10 = LRTF_MFMA(a1, v0, c10);
-                c11 = LRTF_MFMA(a1, v1, c11);
+                c00 = mfma_16x16x4(a0, v0, c00);
+                c01 = mfma_16x16x4(a0, v1, c01);
+                c10 = mfma_16x16x4(a1, v0, c10);
+                c11 = mfma_16x16x4(a1, v1, c11);
             }
         }
         acc[m][0][0] = c00;
@@ -141,10 +138,10 @@ __global__ void __launch_bounds__(kThreads) lrtf_fwd_kernel(Args a, float* __res
                         const float a0 = buf[col * kZStride + kl], a1 = buf[(16 + col) * kZStride + kl];
                         const float* Fr = F + (size_t)(min(k0 + kl, d - 1) + 1) * a.O;
                         const float v0 = Fr[oc0], v1 = Fr[oc1];
-                        c00 = LRTF_MFMA(a0, v0, c00);
-                        c01 = LRTF_MFMA(a0, v1, c01);
-                        c10 = LRTF_MFMA(a1, v0, c10);
-                        c11 = LRTF_MFMA(a1, v1, c11);
+                        c00 = mfma_16x16x4(a0, v0, c00);
+                        c01 = mfma_16x16x4(a0, v1, c01);
+                        c10 = mfma_16x16x4(a1, v0, c10);
+                        c11 = mfma_16x16x4(a1, v1, c11);
                     }
                 }
             }
@@ -255,8 +252,8 @@ __global__ void __launch_bounds__(kThreads) lrtf_bwd_factor_kernel(Args a, const
                     const int bl = 4 * s + kq, b = cb + bl;
                     float av = zm[(size_t)min(b, B - 1) * d + kfc];        // A[row = feature][k = sample]
                     av = (b < B && kf < d) ? av : 0.f;
-                    e0 = LRTF_MFMA(av, dps[m][bl][col], e0);               // B[k = sample][col = output]
-                    e1 = LRTF_MFMA(av, dps[m][bl][16 + col], e1);
+                    e0 = mfma_16x16x4(av, dps[m][bl][col], e0);               // B[k = sample][col = output]
+                    e1 = mfma_16x16x4(av, dps[m][bl][16 + col], e1);
                 }
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg) {
@@ -339,8 +336,8 @@ __global__ void __launch_bounds__(kThreads) lrtf_bwd_input_kernel(Args a, const 
                 for (int s = 0; s < kChunk / 4; ++s) {
                         const int ol = 4 * s + kq;
                         const float bv = Fr[min(co + ol, O - 1)];          // B[k = output][col = feature]; dP is 0 past O
-                        e0 = LRTF_MFMA(dps[m][col][ol], bv, e0);           // A[row = sample][k = output]
-                        e1 = LRTF_MFMA(dps[m][16 + col][ol], bv, e1);
+                        e0 = mfma_16x16x4(dps[m][col][ol], bv, e0);           // A[row = sample][k = output]
+                        e1 = mfma_16x16x4(dps[m][16 + col][ol], bv, e1);
                     }
 #pragma unroll
                     for (int i = 0; i < 2; ++i)

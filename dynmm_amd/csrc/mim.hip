@@ -23,11 +23,10 @@
 //             the g U^T / g V^T slab of mim_lin_bwd_kernel.
 // No floating-point atomics: equal inputs give equal bits.
 #include "common.h"
+#include "mfma.h"
 
 namespace dynmm {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kThreads = 256;
 constexpr int kBT = 128;                   // a workgroup's tile edge
@@ -39,6 +38,7 @@ constexpr int kFwdGroups = 512;
 constexpr int kWgradGroups = 256;          // one workgroup per CU: 132 KB of LDS
 constexpr int kIgradGroups = 512;
 
+// a macro: through mfma.h's inline wrapper the compiler allocates this file's registers differently
 #define MIM_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }

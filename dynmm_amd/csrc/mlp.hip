@@ -337,14 +337,6 @@ using namespace dynmm;
 
 #define ST ((hipStream_t)stream)
 
-static DropSpec mlp_drop_spec(const dynmm_dropout* d) {
-    DropSpec s{};
-    if (d && d->p > 0.f) {
-        s.mask = d->mask; s.step = d->step; s.seed = d->seed; s.offset = d->offset; s.p = d->p;
-    }
-    return s;
-}
-
 extern "C" int dynmm_maxout_bn_fwd(const float* z, float* y, float* save_mean, float* save_rstd, float* running_mean,
                                    float* running_var, long long* num_batches_tracked, const float* gamma, const float* beta,
                                    int B, int M, int maxout, float eps, float momentum, int train, const dynmm_dropout* drop,
@@ -356,7 +348,7 @@ extern "C" int dynmm_maxout_bn_fwd(const float* z, float* y, float* save_mean, f
     if (drop && !(drop->p >= 0.f && drop->p < 1.f)) return DYNMM_EINVAL;
     if (maxout && (((uintptr_t)z) & 7)) return DYNMM_EINVAL;
     const dim3 grid(ceil_div(M, kMoCols));
-    const DropSpec spec = mlp_drop_spec(train ? drop : nullptr);
+    const DropSpec spec = drop_spec(train ? drop : nullptr);
     if (maxout)
         hipLaunchKernelGGL(mo_bn_fwd_kernel<true>, grid, dim3(256), 0, ST, z, y, save_mean, save_rstd, running_mean, running_var,
                            num_batches_tracked, gamma, beta, B, M, eps, momentum, train, spec);
@@ -375,7 +367,7 @@ extern "C" int dynmm_maxout_bn_bwd(const float* dy, const float* z, const float*
     if (drop && !(drop->p >= 0.f && drop->p < 1.f)) return DYNMM_EINVAL;
     if (maxout && ((((uintptr_t)z) & 7) || (((uintptr_t)dz) & 7))) return DYNMM_EINVAL;
     const dim3 grid(ceil_div(M, kMoCols));
-    const DropSpec spec = mlp_drop_spec(train ? drop : nullptr);
+    const DropSpec spec = drop_spec(train ? drop : nullptr);
     if (maxout)
         hipLaunchKernelGGL(mo_bn_bwd_kernel<true>, grid, dim3(256), 0, ST, dy, z, save_mean, save_rstd, gamma, dz, dgamma, dbeta,
                            B, M, train, spec);

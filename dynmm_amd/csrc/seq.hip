@@ -650,15 +650,6 @@ using namespace dynmm;
 
 #define ST ((hipStream_t)stream)
 
-static DropSpec drop_spec(const dynmm_dropout* d) {
-    DropSpec s{};
-    if (d && d->p > 0.f) {
-        s.mask = d->mask; s.step = d->step; s.seed = d->seed; s.offset = d->offset; s.p = d->p;
-    }
-    return s;
-}
-static bool drop_ok(const dynmm_dropout* d) { return !d || (d->p >= 0.f && d->p < 1.f); }
-
 extern "C" int dynmm_dropout_apply(const float* x, float* y, size_t n, const dynmm_dropout* drop, void* stream) {
     (void)hipGetLastError();
     if (!x || !y || n == 0 || !drop_ok(drop)) return DYNMM_EINVAL;

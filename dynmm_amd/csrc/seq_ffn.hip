@@ -21,17 +21,10 @@
 // The weight gradients (contractions over the tokens) stay on the grouped weight-gradient kernels with X / Hd / dH / dOut as
 // 1x1-convolution operands.
 #include "common.h"
+#include "dropout.h"
+#include "mfma.h"
 
 namespace dynmm {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct FfnDrop {
-    const unsigned char* mask;
-    const unsigned long long* step;
-    unsigned long long seed, offset;
-    float p;
-};
 
 struct FfnArgs {
     const float* x;        // forward: layer input [B, D, T]; backward: gradient of the block's output [B, D, T]
@@ -43,21 +36,8 @@ struct FfnArgs {
     float* parts;          // [nsplit][B, D, T]
     int B, D, T, F, nsplit, nfb, ntok;
     float scale;           // backward: 1 / (1 - p)
-    FfnDrop drop;
+    DropSpec drop;
 };
-
-__device__ __forceinline__ void ffn_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                           uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 constexpr int kFfnLd2 = 36;                      // W2 block row: 32 hidden units + 4 (rows 144 B apart: conflict-free b128)
 
@@ -191,11 +171,11 @@ __global__ void __launch_bounds__(256, 2) ffn_kernel(const FfnArgs a) {
                 const float2 a0 = nx[0], a1 = nx[1];
                 if (u + 2 < KS / 2) nx[0] = *reinterpret_cast<const float2*>(ap + 4 * (u + 2));
                 if (u + 3 < KS / 2) nx[1] = *reinterpret_cast<const float2*>(ap + 4 * (u + 3));
-                hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, xr[2 * u], hacc, 0, 0, 0);
-                hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, xr[2 * u + 1], hacc, 0, 0, 0);
+                hacc = mfma_32x32x2(a0.x, xr[2 * u], hacc);
+                hacc = mfma_32x32x2(a0.y, xr[2 * u + 1], hacc);
                 if (u + 1 < KS / 2) {
-                    hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, xr[2 * u + 2], hacc, 0, 0, 0);
-                    hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, xr[2 * u + 3], hacc, 0, 0, 0);
+                    hacc = mfma_32x32x2(a1.x, xr[2 * u + 2], hacc);
+                    hacc = mfma_32x32x2(a1.y, xr[2 * u + 3], hacc);
                 }
             }
         } else {
@@ -213,7 +193,7 @@ __global__ void __launch_bounds__(256, 2) ffn_kernel(const FfnArgs a) {
                     if (s + 4 + e < KS) nx[e] = ap[(4 * ((s + 4 + e) >> 1) + (e & 1)) * kFfnLd2];
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (s + e < KS) hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], xr[s + e], hacc, 0, 0, 0);
+                    if (s + e < KS) hacc = mfma_32x32x2(av[e], xr[s + e], hacc);
             }
         }
 
@@ -231,7 +211,7 @@ __global__ void __launch_bounds__(256, 2) ffn_kernel(const FfnArgs a) {
                 for (int c = 0; c < 2; ++c) {
                     const int fq = f0 + 16 * c + 4 * h;       // first of the two quads (q = 2c, 2c + 1) this call serves
                     const unsigned long long qi = ((unsigned long long)b * (F >> 2) + (fq >> 2)) * T + t;
-                    ffn_philox((uint32_t)qi, (uint32_t)(qi >> 32), (uint32_t)doff, (uint32_t)(doff >> 32), dk0, dk1, rnd[c]);
+                    philox4x32_10((uint32_t)qi, (uint32_t)(qi >> 32), (uint32_t)doff, (uint32_t)(doff >> 32), dk0, dk1, rnd[c]);
                 }
             }
 #pragma unroll
@@ -279,10 +259,10 @@ __global__ void __launch_bounds__(256, 2) ffn_kernel(const FfnArgs a) {
                     const float4 av = nx;
                     if (jq + 1 < NDB * 4)
                         nx = *reinterpret_cast<const float4*>(ap + 32 * ((jq + 1) >> 2) * kFfnLd2 + 8 * ((jq + 1) & 3));
-                    oacc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, hv[4 * q + 0], oacc[j], 0, 0, 0);
-                    oacc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, hv[4 * q + 1], oacc[j], 0, 0, 0);
-                    oacc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, hv[4 * q + 2], oacc[j], 0, 0, 0);
-                    oacc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, hv[4 * q + 3], oacc[j], 0, 0, 0);
+                    oacc[j] = mfma_32x32x2(av.x, hv[4 * q + 0], oacc[j]);
+                    oacc[j] = mfma_32x32x2(av.y, hv[4 * q + 1], oacc[j]);
+                    oacc[j] = mfma_32x32x2(av.z, hv[4 * q + 2], oacc[j]);
+                    oacc[j] = mfma_32x32x2(av.w, hv[4 * q + 3], oacc[j]);
                 }
         } else {
             const float* ap = t1 + 4 * h * LD1 + l32;                         // W1[f0 + fl(r, h)][d = 32 j + l32]
@@ -300,7 +280,7 @@ __global__ void __launch_bounds__(256, 2) ffn_kernel(const FfnArgs a) {
                     for (int j = 0; j < NDB; ++j) nx[j] = ap[fl * LD1 + 32 * j];
                 }
 #pragma unroll
-                for (int j = 0; j < NDB; ++j) oacc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], hv[r], oacc[j], 0, 0, 0);
+                for (int j = 0; j < NDB; ++j) oacc[j] = mfma_32x32x2(av[j], hv[r], oacc[j]);
             }
         }
 
@@ -382,18 +362,14 @@ extern "C" int dynmm_ffn_fwd(const float* x, const float* w1, const float* b1, c
                              float* out_parts, int B, int D, int T, int F, int nsplit, const dynmm_dropout* drop,
                              void* stream) {
     (void)hipGetLastError();
-    if (!x || !w1 || !b1 || !w2 || !hidden || !out_parts) return DYNMM_EINVAL;
-    if (drop && !(drop->p >= 0.f && drop->p < 1.f)) return DYNMM_EINVAL;
+    if (!x || !w1 || !b1 || !w2 || !hidden || !out_parts || !drop_ok(drop)) return DYNMM_EINVAL;
     if (!ffn_geom_ok(B, D, T, F)) return DYNMM_EUNSUPPORTED;
     if (nsplit <= 0 || (F / 32) % nsplit != 0) return DYNMM_EINVAL;
     if ((((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)b1) & 15) != 0) return DYNMM_EUNSUPPORTED;
     FfnArgs a{};
     a.x = x; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.hid_out = hidden; a.parts = out_parts;
     a.B = B; a.D = D; a.T = T; a.F = F; a.nsplit = nsplit; a.nfb = F / 32 / nsplit; a.ntok = B * T; a.scale = 1.f;
-    if (drop && drop->p > 0.f) {
-        a.drop.mask = drop->mask; a.drop.step = drop->step; a.drop.seed = drop->seed; a.drop.offset = drop->offset;
-        a.drop.p = drop->p;
-    }
+    a.drop = drop_spec(drop);
     return launch_ffn<false>(a, (hipStream_t)stream);
 }
 

@@ -56,6 +56,15 @@ IMDB_FUSE = {0: 'ef', 1: 'lf', 2: 'lrtf', 3: 'mim'}
 AFFECT_FUSION = {0: 'ef_gru', 1: 'lf_gru', 2: 'ef_tran', 3: 'lf_tran', 4: 'mult', 5: 'lrtf'}
 
 
+def _not_wired(switch, model, where):
+    """The refusal of a command-line switch whose model is built by a function of its own."""
+    return NotImplementedError(f'{switch}: the driver switch is not wired yet; the {model} itself runs on the HIP path: {where}')
+
+
+_FUSION_5 = ('affect_mm --fusion 5 (lrtf)', 'LowRankTensorFusion model over GRUWithLinear encoders',
+             'dynmm_amd.nn.affect.low_rank_fusion_gru, experts.affect_mm_lrtf')
+
+
 def imdb_uni(mod):
     """imdb_uni.py: (encoder, head) of modality `mod` (0 text, 1 image)."""
     if mod not in (0, 1):
@@ -80,8 +89,9 @@ def imdb_mm(fuse):
             model, lr = I.MMDL([Identity(), Identity()], I.Concat(), I.MaxOut_MLP(I.NUM_CLASSES, 512, 4396)), 4e-2
         return _tag_maxout(model), lr
     if fuse in (2, 3):
-        missing = 'LowRankTensorFusion' if fuse == 2 else 'MultiplicativeInteractions2Modal'
-        raise NotImplementedError(f'imdb_mm --fuse {fuse} ({IMDB_FUSE[fuse]}): {missing} has no HIP kernels')
+        fusion = 'LowRankTensorFusion' if fuse == 2 else 'MultiplicativeInteractions2Modal'
+        raise _not_wired(f'imdb_mm --fuse {fuse} ({IMDB_FUSE[fuse]})', f'{fusion} model',
+                         f'dynmm_amd.nn.imdb.{fusion}, experts.imdb_mm_{IMDB_FUSE[fuse]}')
     raise ValueError(f'--fuse {fuse}: one of 0-3')
 
 
@@ -100,9 +110,7 @@ def imdb_mm_mim(output_dim=1024):
 def affect_uni(mod, enc='transformer', hidden_dim1=0, hidden_dim2=0, clf=False):
     """affect_uni.py: (encoder, head, modality name) of modality `mod` (0 visual, 1 audio, 2 text)."""
     if enc != 'transformer':
-        raise NotImplementedError(f'--enc {enc}: the driver switch is not wired yet (only --enc transformer runs from the '
-                                  f'command line); the GRU expert itself runs on the HIP path: dynmm_amd.nn.affect.GRU, '
-                                  f'experts.affect_uni_gru')
+        raise _not_wired(f'--enc {enc}', 'GRU expert', 'dynmm_amd.nn.affect.GRU, experts.affect_uni_gru')
     if clf:
         raise NotImplementedError('--clf: the 2-output posneg-clf head trains with CrossEntropyLoss, which has no HIP '
                                   'objective kernel (only the regression head with L1Loss runs)')
@@ -121,18 +129,15 @@ def affect_mm(fusion):
     if fusion == 3:
         return A.late_fusion_transformer()
     if fusion in (0, 1):
-        raise NotImplementedError(f'affect_mm --fusion {fusion} ({AFFECT_FUSION[fusion]}): the driver switch is not wired yet; '
-                                  f'the GRU model itself runs on the HIP path: dynmm_amd.nn.affect.GRU, '
-                                  f'experts.affect_mm_gru')
+        raise _not_wired(f'affect_mm --fusion {fusion} ({AFFECT_FUSION[fusion]})', 'GRU model',
+                         'dynmm_amd.nn.affect.GRU, experts.affect_mm_gru')
     if fusion == 5:
-        raise NotImplementedError('affect_mm --fusion 5 (lrtf): LowRankTensorFusion over GRUWithLinear encoders has no HIP '
-                                  'kernels')
+        raise _not_wired(*_FUSION_5)
     if fusion == 4:
         raise NotImplementedError('affect_mm --fusion 4 (mult): MULTModel has no HIP kernels')
     if fusion == 2:
-        raise NotImplementedError('affect_mm --fusion 2 (ef_tran): the driver switch is not wired yet; the early-fusion '
-                                  'Transformer(409, 300) model itself runs on the HIP path: '
-                                  'dynmm_amd.nn.affect.early_fusion_transformer, experts.affect_mm_ef_tran')
+        raise _not_wired('affect_mm --fusion 2 (ef_tran)', 'early-fusion Transformer(409, 300) model',
+                         'dynmm_amd.nn.affect.early_fusion_transformer, experts.affect_mm_ef_tran')
     raise ValueError(f'--fusion {fusion}: one of 0-5')
 
 
@@ -158,7 +163,7 @@ def affect_mm_gru(fusion):
     if fusion == 0:
         return A.early_fusion_gru()
     if fusion == 5:
-        raise NotImplementedError('affect_mm --fusion 5 (lrtf): LowRankTensorFusion has no HIP kernels')
+        raise _not_wired(*_FUSION_5)
     raise ValueError(f'affect_mm_gru({fusion}): 0 (ef_gru) or 1 (lf_gru)')
 
 

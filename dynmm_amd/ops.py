@@ -44,6 +44,19 @@ def _chk(t, name='tensor'):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _operand(op, t, name, shape=None):
+    """a device, float32, contiguous operand of operator `op` (refused otherwise: the gradients are written in the operands' own
+    layout)"""
+    if not torch.is_tensor(t):
+        raise L.DynmmHipError(f'{op}: {name} must be a tensor, got {type(t).__name__}')
+    _chk(t, name)
+    if not t.is_contiguous():
+        raise L.DynmmHipError(f'{op}: {name} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}')
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise L.DynmmHipError(f'{op}: {name} must be {tuple(shape)}, got {tuple(t.shape)}')
+    return t
+
+
 # Winograd convolutions on the fp32 matrix cores: the stride-1 1x3 / 3x1 convolutions by 1-D F(2,3) (csrc/conv_wino.hip: 2/3 of the
 # direct matrix work), the 3x3 ones by 2-D F(2x2,3x3) (csrc/conv_wino2d.hip: 4/9) — forward (training and inference) and input
 # gradients of every convolution the kernels' geometry rules admit; the weight gradients by the three-tap form of

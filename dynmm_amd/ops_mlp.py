@@ -14,11 +14,7 @@ from torch.autograd import Function
 
 from . import lib as L
 from . import ops_seq as S
-from .ops import _chk, _grad_dst, _grads_enqueued, _lib, _p, _ptr_array, _stream
-
-
-def _drop_arg(d):
-    return C.byref(d.desc()) if d is not None and d.p > 0 else None
+from .ops import _chk, _grad_dst, _grads_enqueued, _lib, _operand, _p, _ptr_array, _stream
 
 
 def _bn_stats_ptrs(bn):
@@ -53,7 +49,7 @@ class _MaxoutBN(Function):
         L.check(lib.dynmm_maxout_bn_fwd(_p(z), _p(y), _p(mean), _p(rstd), _p(rm) if update or not train else None,
                                         _p(rv) if update or not train else None, _p(nbt) if update else None,
                                         _p(_chk(gamma, 'gamma')), _p(_chk(beta, 'beta')), B, M, int(bool(maxout)),
-                                        float(bn.eps), float(bn.momentum), int(train), _drop_arg(drop), _stream()),
+                                        float(bn.eps), float(bn.momentum), int(train), S._drop_arg(drop), _stream()),
                 'maxout_bn_fwd')
         ctx.save_for_backward(z, mean, rstd, gamma)
         ctx.params = (gamma, beta)
@@ -73,7 +69,7 @@ class _MaxoutBN(Function):
             dg, dg_ret = _grad_dst(ctx.params[0])
             db, db_ret = _grad_dst(ctx.params[1])
         L.check(lib.dynmm_maxout_bn_bwd(_p(g), _p(z), _p(mean), _p(rstd), _p(gamma), _p(dz), _p(dg), _p(db), B, M,
-                                        int(ctx.maxout), int(ctx.train), _drop_arg(ctx.drop), _stream()), 'maxout_bn_bwd')
+                                        int(ctx.maxout), int(ctx.train), S._drop_arg(ctx.drop), _stream()), 'maxout_bn_bwd')
         _grads_enqueued()
         return dz, dg_ret, db_ret, None, None, None
 
@@ -93,18 +89,6 @@ def maxout_bn(z, bn, drop=None, maxout=True):
 # ---------------------------------------------------------------------------------------------------------------
 # multiplicative interactions fusion (MultiBench fusions.common_fusions.MultiplicativeInteractions2Modal), csrc/mim.hip
 # ---------------------------------------------------------------------------------------------------------------
-def _mim_operand(t, name, shape=None):
-    """a device, float32, contiguous operand (refused otherwise: the gradients are written in the operands' own layout)"""
-    if not torch.is_tensor(t):
-        raise L.DynmmHipError(f'mim: {name} must be a tensor, got {type(t).__name__}')
-    _chk(t, name)
-    if not t.is_contiguous():
-        raise L.DynmmHipError(f'mim: {name} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}')
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise L.DynmmHipError(f'mim: {name} must be {tuple(shape)}, got {tuple(t.shape)}')
-    return t
-
-
 class _MIM(Function):
     """out [B, D] of (m1, m2, W, U, V, b).  Saves its inputs only."""
 
@@ -155,14 +139,14 @@ def mim(m1, m2, W, U, V, b):
     """MultiBench's MultiplicativeInteractions2Modal(output='matrix') on m1 [B, n], m2 [B, m]:
     out = einsum('bm,bmd->bd', m2, einsum('bn,nmd->bmd', m1, W) + V) + m1 @ U + b -> [B, D], with W [n, m, D], U [n, D],
     V [m, D], b [D].  One operator forward and backward (csrc/mim.hip); no [B, m, D] tensor exists."""
-    m1, m2 = _mim_operand(m1, 'm1'), _mim_operand(m2, 'm2')
+    m1, m2 = _operand('mim', m1, 'm1'), _operand('mim', m2, 'm2')
     if m1.dim() != 2 or m2.dim() != 2 or m1.shape[0] != m2.shape[0]:
         raise L.DynmmHipError(f'mim: m1 [B, n] and m2 [B, m] must share B, got {tuple(m1.shape)} and {tuple(m2.shape)}')
     if not torch.is_tensor(W) or W.dim() != 3:
         raise L.DynmmHipError(f'mim: W must be [n, m, D], got {tuple(W.shape) if torch.is_tensor(W) else type(W).__name__}')
     n, m, D = m1.shape[1], m2.shape[1], W.shape[2]
-    W = _mim_operand(W, 'W', (n, m, D))
-    U, V, b = _mim_operand(U, 'U', (n, D)), _mim_operand(V, 'V', (m, D)), _mim_operand(b, 'b', (D,))
+    W = _operand('mim', W, 'W', (n, m, D))
+    U, V, b = _operand('mim', U, 'U', (n, D)), _operand('mim', V, 'V', (m, D)), _operand('mim', b, 'b', (D,))
     if 0 in (m1.shape[0], n, m, D):
         raise L.DynmmHipError(f'mim: empty operands (B, n, m, D) = {(m1.shape[0], n, m, D)}')
     return _MIM.apply(m1, m2, W, U, V, b)
@@ -253,16 +237,7 @@ def ml_loss_backward(logits, preds, target, temp, hard, reg):
     L.check(lib.dynmm_ml_head(_p(logits.detach()), _ptr_array([f.detach() for f in flat]), K, Cc, _p(tgt), float(temp),
                               int(bool(hard)), float(reg), _p(out), _p(weight), _p(scal), arr, _p(dl), B, _stream()),
             'ml_head')
-    roots, grads = [], []
-    for p, d in zip(preds, dps):
-        if d is not None:
-            roots.append(p)
-            grads.append(d)
-    if logits.requires_grad:
-        roots.append(logits)
-        grads.append(dl)
-    if roots:
-        torch.autograd.backward(roots, grads)
+    S._seed_backward(logits, preds, dps, dl)
     return {'out': out, 'weight': weight, 'loss1': scal[0:1], 'aux': scal[1:2], 'total': scal[2:3]}
 
 

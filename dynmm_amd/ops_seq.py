@@ -12,7 +12,7 @@ from torch.autograd import Function
 
 from . import lib as L
 from . import ops
-from .ops import _chk, _grad_dst, _grads_enqueued, _lib, _p, _ptr_array, _stream
+from .ops import _chk, _grad_dst, _grads_enqueued, _lib, _operand, _p, _ptr_array, _stream
 
 
 def linear_bdt(x, weight, bias=None, act=None, defer_mask=False, mask_input=False, link=None):
@@ -38,7 +38,7 @@ def linear_bdt(x, weight, bias=None, act=None, defer_mask=False, mask_input=Fals
 # dropout (nn.TransformerEncoderLayer trains with p = 0.1 at four sites per layer)
 # ---------------------------------------------------------------------------------------------------------------
 # A site is an integer; its keep decisions are Philox(seed, (site << 32) + device step counter, element index)
-# (csrc/seq.hip): nothing is stored for the backward, and a captured step draws new masks at every replay because the
+# (csrc/dropout.h): nothing is stored for the backward, and a captured step draws new masks at every replay because the
 # counter lives on the device (advance_dropout_step(), called once per training step).
 MASKS = None            # tests: callable(site_name, shape) -> uint8 keep flags (device tensor) or None
 _SITE_IDS = itertools.count(1)
@@ -392,18 +392,6 @@ def gru_seq(x, w_ih, w_hh, b_ih, b_hh, lengths=None, arm=None):
 # ---------------------------------------------------------------------------------------------------------------
 # low-rank tensor fusion (MultiBench fusions.common_fusions.LowRankTensorFusion), csrc/lrtf.hip
 # ---------------------------------------------------------------------------------------------------------------
-def _lrtf_operand(t, name, shape=None):
-    """a device, float32, contiguous operand (refused otherwise: the gradients are written in the operands' own layout)"""
-    if not torch.is_tensor(t):
-        raise L.DynmmHipError(f'lrtf: {name} must be a tensor, got {type(t).__name__}')
-    _chk(t, name)
-    if not t.is_contiguous():
-        raise L.DynmmHipError(f'lrtf: {name} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}')
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise L.DynmmHipError(f'lrtf: {name} must be {tuple(shape)}, got {tuple(t.shape)}')
-    return t
-
-
 class _LRTF(Function):
     """out [B, O] of (fusion_weights [1, R], fusion_bias [1, O], z_0 .. z_{M-1}, F_0 .. F_{M-1}).  Saves its inputs only: the
     backward recomputes every P_m."""
@@ -475,91 +463,71 @@ def lrtf(zs, factors, fusion_weights, fusion_bias):
     if M not in (2, 3) or len(factors) != M:
         raise L.DynmmHipError(f'lrtf: M = {M} inputs with {len(factors)} factors: the kernels serve M = 2 or 3 modalities, one '
                               f'factor each')
-    zs = [_lrtf_operand(z, f'z[{m}]') for m, z in enumerate(zs)]
+    zs = [_operand('lrtf', z, f'z[{m}]') for m, z in enumerate(zs)]
     if any(z.dim() != 2 or z.shape[0] != zs[0].shape[0] for z in zs):
         raise L.DynmmHipError(f'lrtf: inputs must be [B, d_m] with one B, got {[tuple(z.shape) for z in zs]}')
     if factors[0].dim() != 3:
         raise L.DynmmHipError(f'lrtf: factors[0] must be [R, d_0 + 1, O], got {tuple(factors[0].shape)}')
     R, O = factors[0].shape[0], factors[0].shape[2]
-    factors = [_lrtf_operand(f, f'factors[{m}]', (R, zs[m].shape[1] + 1, O)) for m, f in enumerate(factors)]
-    w = _lrtf_operand(fusion_weights, 'fusion_weights', (1, R))
-    bias = _lrtf_operand(fusion_bias, 'fusion_bias', (1, O))
+    factors = [_operand('lrtf', f, f'factors[{m}]', (R, zs[m].shape[1] + 1, O)) for m, f in enumerate(factors)]
+    w = _operand('lrtf', fusion_weights, 'fusion_weights', (1, R))
+    bias = _operand('lrtf', fusion_bias, 'fusion_bias', (1, O))
     return _LRTF.apply(w, bias, M, *zs, *factors)
 
 
-class _MHACore(Function):
-    @staticmethod
+def _mha_function(name, fwd, bwd, fwd_label, bwd_label, doc=None):
+    """The autograd Function of an attention core: out [B, D, T] of (qkv [B, 3D, T], heads, drop) through the library's entry
+    points `fwd` / `bwd`, which share one argument list."""
+
     def forward(ctx, qkv, heads, drop=None):
-        lib = _lib()
         qkv = _chk(qkv, 'qkv')
         B, D3, T = qkv.shape
         D = D3 // 3
         out = torch.empty((B, D, T), device=qkv.device, dtype=torch.float32)
         probs = torch.empty((B * heads, T, T), device=qkv.device, dtype=torch.float32)
-        L.check(lib.dynmm_mha_drop_fwd(_p(qkv), _p(out), _p(probs), B, D, T, heads, _drop_arg(drop), _stream()), 'mha_fwd')
+        L.check(getattr(_lib(), fwd)(_p(qkv), _p(out), _p(probs), B, D, T, heads, _drop_arg(drop), _stream()), fwd_label)
         ctx.drop = drop
         ctx.save_for_backward(qkv, probs)
         ctx.heads = heads
         return out
 
-    @staticmethod
     def backward(ctx, g):
-        lib = _lib()
         qkv, probs = ctx.saved_tensors
         g = _chk(g, 'grad')
         B, D3, T = qkv.shape
         dqkv = torch.empty_like(qkv)
-        L.check(lib.dynmm_mha_drop_bwd(_p(g), _p(qkv), _p(probs), _p(dqkv), B, D3 // 3, T, ctx.heads, _drop_arg(ctx.drop),
-                                       _stream()), 'mha_bwd')
+        L.check(getattr(_lib(), bwd)(_p(g), _p(qkv), _p(probs), _p(dqkv), B, D3 // 3, T, ctx.heads, _drop_arg(ctx.drop),
+                                     _stream()), bwd_label)
         return dqkv, None, None
+
+    return type(name, (Function,), {'forward': staticmethod(forward), 'backward': staticmethod(backward), '__doc__': doc,
+                                    '__module__': __name__})
+
+
+_MHACore = _mha_function('_MHACore', 'dynmm_mha_drop_fwd', 'dynmm_mha_drop_bwd', 'mha_fwd', 'mha_bwd')
+_MHAWide = _mha_function('_MHAWide', 'dynmm_attn_fwd', 'dynmm_attn_bwd', 'attn_fwd', 'attn_bwd',
+                         "_MHACore's contract on the matrix-core kernels of csrc/attn.hip (head dimensions up to 64).")
+
+MHA_CORE_MAX_DH = 32     # csrc/seq.hip: kSeqMaxDh
+
+
+def _probs_drop(qkv, heads, drop):
+    """the Drop of the [B*heads, T, T] attention probabilities; drop = (p, site, name) or None"""
+    if drop is None or not drop[0] > 0:
+        return None
+    return Drop(drop[0], drop[1], drop[2], (qkv.shape[0] * heads, qkv.shape[2], qkv.shape[2]), qkv.device)
 
 
 def mha_core(qkv, heads, drop=None):
     """dropout(softmax(q k^T / sqrt(dh))) v per head for qkv [B, 3D, T] (q | k | v along channels) -> [B, D, T];
     drop = (p, site, name) or None: dropout on the [B*heads, T, T] probabilities."""
-    B, D3, T = qkv.shape
-    d = Drop(drop[0], drop[1], drop[2], (B * heads, T, T), qkv.device) if drop is not None and drop[0] > 0 else None
-    return _MHACore.apply(qkv, heads, d)
-
-
-MHA_CORE_MAX_DH = 32     # csrc/seq.hip: kSeqMaxDh
-
-
-class _MHAWide(Function):
-    """_MHACore's contract on the matrix-core kernels of csrc/attn.hip (head dimensions up to 64)."""
-
-    @staticmethod
-    def forward(ctx, qkv, heads, drop=None):
-        lib = _lib()
-        qkv = _chk(qkv, 'qkv')
-        B, D3, T = qkv.shape
-        D = D3 // 3
-        out = torch.empty((B, D, T), device=qkv.device, dtype=torch.float32)
-        probs = torch.empty((B * heads, T, T), device=qkv.device, dtype=torch.float32)
-        L.check(lib.dynmm_attn_fwd(_p(qkv), _p(out), _p(probs), B, D, T, heads, _drop_arg(drop), _stream()), 'attn_fwd')
-        ctx.drop = drop
-        ctx.save_for_backward(qkv, probs)
-        ctx.heads = heads
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib()
-        qkv, probs = ctx.saved_tensors
-        g = _chk(g, 'grad')
-        B, D3, T = qkv.shape
-        dqkv = torch.empty_like(qkv)
-        L.check(lib.dynmm_attn_bwd(_p(g), _p(qkv), _p(probs), _p(dqkv), B, D3 // 3, T, ctx.heads, _drop_arg(ctx.drop),
-                                   _stream()), 'attn_bwd')
-        return dqkv, None, None
+    return _MHACore.apply(qkv, heads, _probs_drop(qkv, heads, drop))
 
 
 def mha_wide(qkv, heads, drop=None):
     """mha_core for head dimensions up to 64 (T <= 64): the same function, arguments and dropout site (name, shape
     (B*heads, T, T), indexing, generator decisions) on 16x16 fp32 matrix-core tiles (csrc/attn.hip)."""
-    B, D3, T = qkv.shape
-    d = Drop(drop[0], drop[1], drop[2], (B * heads, T, T), qkv.device) if drop is not None and drop[0] > 0 else None
-    return _MHAWide.apply(qkv, heads, d)
+    return _MHAWide.apply(qkv, heads, _probs_drop(qkv, heads, drop))
 
 
 def attention(qkv, heads, drop=None):
@@ -608,6 +576,18 @@ def moe_blend(logits, preds, temp=1.0, hard=False):
     return _MoEBlend.apply(logits, temp, hard, *preds)
 
 
+def _seed_backward(logits, preds, dps, dl):
+    """The tail of a mixture's fused loss: start the backward pass from the kernel's seeds, dps[k] for every prediction that
+    requires grad (None for the others) and dl for the logits."""
+    roots = [p for p, d in zip(preds, dps) if d is not None]
+    grads = [d.reshape(p.shape) for p, d in zip(preds, dps) if d is not None]
+    if logits.requires_grad:
+        roots.append(logits)
+        grads.append(dl)
+    if roots:
+        torch.autograd.backward(roots, grads)
+
+
 def moe_loss_backward(logits, preds, target, temp, hard, reg):
     """Supervised_Learning.py:120-141 for a DynMM mixture, on the device: blend, L1 loss, loss1 + reg * aux, and the
     backward pass seeded straight from the kernel (no PyTorch arithmetic kernels).  Returns
@@ -624,16 +604,7 @@ def moe_loss_backward(logits, preds, target, temp, hard, reg):
     arr = (C.c_void_p * K)(*[(None if d is None else d.data_ptr()) for d in dps])
     L.check(lib.dynmm_moe_head(_p(logits.detach()), _ptr_array(flat), K, _p(tgt), float(temp), int(bool(hard)), float(reg),
                                _p(out), _p(weight), _p(scal), arr, _p(dl), B, _stream()), 'moe_head')
-    roots, grads = [], []
-    for p, d in zip(preds, dps):
-        if d is not None:
-            roots.append(p)
-            grads.append(d.reshape(p.shape))
-    if logits.requires_grad:
-        roots.append(logits)
-        grads.append(dl)
-    if roots:
-        torch.autograd.backward(roots, grads)
+    _seed_backward(logits, preds, dps, dl)
     return {'out': out.reshape(B, 1), 'weight': weight, 'loss1': scal[0:1], 'aux': scal[1:2], 'total': scal[2:3]}
 
 

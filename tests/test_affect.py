@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.parity import Masks as _Masks, rel as _rel
+
 
 def test_state_dict_layout_matches_oracle():
     from dynmm_amd.nn import affect as A
@@ -18,22 +20,6 @@ def test_state_dict_layout_matches_oracle():
     assert all(p.requires_grad == n.startswith('gate') for n, p in v2.named_parameters())
     with pytest.raises(NotImplementedError):
         A.DynMMNetV2(model_name_list=['b1.pt', 'b2.pt'])
-
-
-class _Masks:
-    """The n-th dropout site of a forward pass keeps element e iff rand_n(e) >= p: one deterministic stream both sides
-    walk in the same order (gate, experts; per layer: attn, dropout1, dropout, dropout2)."""
-
-    def __init__(self, p, seed, device='cpu'):
-        self.p, self.seed, self.n, self.device = p, seed, 0, device
-        self.names = []
-
-    def __call__(self, name, shape):
-        g = torch.Generator().manual_seed(self.seed * 100003 + self.n)
-        self.n += 1
-        self.names.append(name)
-        m = (torch.rand(shape, generator=g) >= self.p).to(torch.uint8)
-        return m.to(self.device)
 
 
 def test_oracle_dropout_layer_is_torchs_layer():
@@ -67,11 +53,6 @@ def test_oracle_dropout_layer_is_torchs_layer():
     it = iter(served)
     got = O.encoder_layer_dropout(layer, x, p, lambda name, shape: torch.full(shape, 1.0 - p) if name == 'attn' else next(it))
     assert len(served) == 3 and _rel(got, want) < 1e-6
-
-
-def _rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
 
 
 @pytest.mark.gpu

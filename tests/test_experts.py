@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from tests import imdb_oracle as IO
+from tests.parity import Masks as _Masks, check_adam_params, randomize_bn
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -259,30 +260,6 @@ def test_head_loss_kernel_against_fp64(kind, B, C):
     assert s3 is None and torch.equal(l3, loss)
 
 
-class _Masks:
-    """The n-th dropout site of a forward pass keeps element e iff rand_n(e) >= p (one stream both sides walk in order)."""
-
-    def __init__(self, p, seed, device='cpu'):
-        self.p, self.seed, self.n, self.device = p, seed, 0, device
-
-    def __call__(self, name, shape):
-        g = torch.Generator().manual_seed(self.seed * 100003 + self.n)
-        self.n += 1
-        return (torch.rand(shape, generator=g) >= self.p).to(torch.uint8).to(self.device)
-
-
-def _randomize_bn(model, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    for m in model.modules():
-        if isinstance(m, nn.BatchNorm1d):
-            n = m.num_features
-            with torch.no_grad():
-                m.weight.copy_(1 + 0.2 * torch.randn(n, generator=g))
-                m.bias.copy_(0.2 * torch.randn(n, generator=g))
-                m.running_mean.copy_(0.1 * torch.randn(n, generator=g))
-                m.running_var.copy_(0.5 + torch.rand(n, generator=g))
-
-
 def _imdb_pair(kind):
     """(mine, oracle fp64, input adapter) of an MM-IMDB expert kind."""
     from dynmm_amd import experts as E
@@ -301,22 +278,9 @@ def _imdb_pair(kind):
         mine, _ = E.imdb_mm(0)
         ref = IO.MMDL([nn.Identity(), nn.Identity()], IO.Concat(), IO.MaxOut_MLP(23, 512, 4396, tag='head'))
         adapt = lambda x: x                                                   # noqa: E731
-    _randomize_bn(ref, 3)
+    randomize_bn(ref, 3)
     mine.load_state_dict(ref.state_dict())
     return mine.cuda(), ref.double(), adapt
-
-
-def _check_params(mine, ref, names, lr, tag):
-    # Adam's first updates are lr * sign(g) whatever |g|: an element whose gradient is rounding noise can move the other way
-    # (2 update sizes apart).  Almost every element must agree to a fraction of an update, none further than two.
-    sd, sd_r = mine.state_dict(), ref.state_dict()
-    for k in names:
-        d = (sd[k].cpu().double() - sd_r[k].double()).abs()
-        if k.endswith('in_proj_bias'):
-            third = d.numel() // 3                 # the key bias has an analytically zero gradient: rounding noise both sides
-            d = torch.cat([d[:third], d[2 * third:]])
-        n_far = int((d > 0.2 * 2 * lr).sum().item())
-        assert n_far <= max(1, int(2e-3 * d.numel())) and d.max().item() < 2.2 * 2 * lr, (tag, k, n_far, d.max().item())
 
 
 @pytest.mark.gpu
@@ -363,7 +327,7 @@ def test_imdb_expert_train_step_against_oracle(kind):
         IO.MASKS.clear()
     torch.cuda.synchronize()
     step.opt.check_finite()
-    _check_params(mine, ref, names, lr, kind)
+    check_adam_params(mine, ref, lr, kind, names)
     sd, sd_r = mine.state_dict(), ref.state_dict()
     for k in sd:
         if 'running_' in k:
@@ -428,7 +392,7 @@ def test_affect_expert_train_step_against_oracle(kind):
         O.Transformer.dropout_masks = None
         S.MASKS = None
     step.opt.check_finite()
-    _check_params(mine, ref, names, lr, kind)
+    check_adam_params(mine, ref, lr, kind, names)
 
 
 @pytest.mark.gpu

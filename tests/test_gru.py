@@ -32,17 +32,13 @@ from dynmm_amd import experts as E
 from dynmm_amd import lib as L
 from dynmm_amd import ops_seq as S
 from dynmm_amd.nn import affect as A
+from tests.parity import check_adam_params, compare_to_float64, rel as _rel
 
 FWD, BWD = 1e-5, 2e-5                         # test_seq_kernels.py: LN_FWD, LN_BWD
 NAMES = ('h_n', 'seq', 'dx', 'dW_ih', 'dW_hh', 'db_ih', 'db_hh')
 
 SHAPES = [(1, 1, 3, 16), (5, 7, 35, 20), (17, 9, 74, 64), (33, 6, 10, 128), (3, 4, 5, 272), (18, 3, 5, 40)]
 BIG = (32, 50, 300, 512)
-
-
-def _rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
 
 
 def gru_ref(x, w_ih, w_hh, b_ih, b_hh, lengths=None):
@@ -121,20 +117,8 @@ def _gpu(shape, with_len, arm):
 
 
 def _compare(tag, got, ref64, ref32, with_len):
-    bad = []
-    for k in NAMES:
-        if k == 'seq' and with_len:
-            assert got[k] is None
-            continue
-        project = FWD if k in ('h_n', 'seq') else BWD
-        assert tuple(got[k].shape) == tuple(ref64[k].shape), (tag, k)
-        err, yard = _rel(got[k], ref64[k]), _rel(ref32[k], ref64[k])
-        bar = max(project, 4.0 * yard)
-        finite = bool(torch.isfinite(got[k]).all())
-        print(f'FIG {tag} {k} kernel={err:.3e} f32={yard:.3e} bar={bar:.3e}' + (' RAISED' if err >= project else ''))
-        if not (finite and err < bar):
-            bad.append((k, err, yard, bar, finite))
-    assert not bad, (tag, bad)
+    assert tuple(ref64) == NAMES
+    compare_to_float64(tag, got, ref64, ref32, ('h_n', 'seq'), FWD, BWD, absent=('seq',) if with_len else ())
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -404,18 +388,6 @@ def _batch(B, T, seed):
     return [xs, [ln] * 3], torch.randn(B, 1, generator=g)
 
 
-def _check_params(mine, ref, lr, tag):
-    """tests/test_experts.py:309-319 (`_check_params`, the transformer experts' step): Adam's first update is lr * sign(g), so
-    an element whose gradient is rounding noise may move the other way; almost every element agrees to a fraction of an
-    update (at most max(1, 2e-3 n) further than 0.2 * 2 lr), none further than 2.2 * 2 lr."""
-    sd, sd_r = mine.state_dict(), ref.state_dict()
-    assert sorted(sd) == sorted(sd_r)
-    for k in sd:
-        d = (sd[k].cpu().double() - sd_r[k].double()).abs()
-        n_far = int((d > 0.2 * 2 * lr).sum().item())
-        assert n_far <= max(1, int(2e-3 * d.numel())) and d.max().item() < 2.2 * 2 * lr, (tag, k, n_far, d.max().item())
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('kind', ['uni', 'lf_gru'])
 def test_expert_train_step_against_torch_gru(kind):
@@ -445,7 +417,7 @@ def test_expert_train_step_against_torch_gru(kind):
     assert abs(last['loss'].item() - loss_r.item()) < 1e-5
     assert abs(last['grad_norm'].item() - gn.item()) < 1e-4 * gn.item()
     step.opt.check_finite()
-    _check_params(mine, ref, lr, kind)
+    check_adam_params(mine, ref, lr, kind)
 
 
 @pytest.mark.gpu

@@ -15,25 +15,9 @@ import torch
 import torch.nn as nn
 
 from tests import imdb_oracle as O
+from tests.parity import randomize_bn, rel
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
-
-
-def randomize_bn(model, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    for m in model.modules():
-        if isinstance(m, nn.BatchNorm1d):
-            n = m.num_features
-            with torch.no_grad():
-                m.weight.copy_(1 + 0.2 * torch.randn(n, generator=g))
-                m.bias.copy_(0.2 * torch.randn(n, generator=g))
-                m.running_mean.copy_(0.1 * torch.randn(n, generator=g))
-                m.running_var.copy_(0.5 + torch.rand(n, generator=g))
 
 
 def inputs(B, seed=0):

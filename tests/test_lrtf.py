@@ -18,7 +18,8 @@ from dynmm_amd import lib as L
 from dynmm_amd import ops_seq as S
 from dynmm_amd.nn import affect as A
 from dynmm_amd.nn import imdb as I
-from tests.test_gru import _RefMLP, _batch, _lengths, _rel, gru_ref
+from tests.parity import Masks as _Masks, check_adam_params, compare_to_float64, randomize_bn, rel as _rel
+from tests.test_gru import _RefMLP, _batch, _lengths, gru_ref
 
 FWD, BWD = 1e-5, 2e-5                         # test_seq_kernels.py: LN_FWD, LN_BWD
 
@@ -91,20 +92,6 @@ def _ref(shape, init):
         c = _case(shape, init)
         _REF[key] = (c, _run(lrtf_ref, c, torch.float64), _run(lrtf_ref, c, torch.float32))
     return _REF[key]
-
-
-def _compare(tag, got, ref64, ref32):
-    bad = []
-    for k in ref64:
-        project = FWD if k == 'out' else BWD
-        assert tuple(got[k].shape) == tuple(ref64[k].shape), (tag, k)
-        err, yard = _rel(got[k], ref64[k]), _rel(ref32[k], ref64[k])
-        bar = max(project, 4.0 * yard)
-        finite = bool(torch.isfinite(got[k]).all())
-        print(f'FIG {tag} {k} kernel={err:.3e} f32={yard:.3e} bar={bar:.3e}' + (' RAISED' if err >= project else ''))
-        if not (finite and err < bar):
-            bad.append((k, err, yard, bar, finite))
-    assert not bad, (tag, bad)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -237,7 +224,7 @@ def _ids(s):
 @pytest.mark.parametrize('shape', SHAPES, ids=_ids)
 def test_lrtf_against_float64(shape, init):
     c, r64, r32 = _ref(shape, init)
-    _compare(f'{_ids(shape)} {init}', _run(S.lrtf, c, torch.float32, 'cuda'), r64, r32)
+    compare_to_float64(f'{_ids(shape)} {init}', _run(S.lrtf, c, torch.float32, 'cuda'), r64, r32, ('out',), FWD, BWD)
 
 
 @pytest.mark.gpu
@@ -245,7 +232,7 @@ def test_lrtf_at_the_full_mm_imdb_geometry():
     c = _case(FULL, 'unit')
     r64 = _run(lrtf_ref, c, torch.float64)
     r32 = _run(lrtf_ref, c, torch.float32)
-    _compare(f'{_ids(FULL)} unit', _run(S.lrtf, c, torch.float32, 'cuda'), r64, r32)
+    compare_to_float64(f'{_ids(FULL)} unit', _run(S.lrtf, c, torch.float32, 'cuda'), r64, r32, ('out',), FWD, BWD)
 
 
 @pytest.mark.gpu
@@ -394,7 +381,6 @@ class _RefMosei(nn.Module):
 def test_affect_lrtf_train_step_against_oracle():
     """Two steps in training mode, dropout p = 0.1 on every encoder's h_n with the same keep flags on both sides."""
     from oracle import affect_oracle as O
-    from tests.test_experts import _Masks, _check_params
     torch.manual_seed(12)
     ref, mine = _RefMosei(), E.affect_mm_lrtf()
     mine.load_state_dict(ref.state_dict(), strict=True)
@@ -426,20 +412,19 @@ def test_affect_lrtf_train_step_against_oracle():
     finally:
         _RefGRUWithLinear.masks, S.MASKS = None, prev
     step.opt.check_finite()
-    _check_params(mine, ref, names, lr, 'affect_lrtf')
+    check_adam_params(mine, ref, lr, 'affect_lrtf', names)
 
 
 @pytest.mark.gpu
 def test_imdb_lrtf_train_step_against_oracle():
     """Two steps at batch 128 with rank 16: BatchNorm in training mode, dropout p = 0.3 with injected keep flags."""
     from tests import imdb_oracle as IO
-    from tests.test_experts import _check_params, _randomize_bn
     torch.manual_seed(5)
     mine, _ = E.imdb_mm_lrtf(rank=16)
     ref = IO.MMDL([IO.MaxOut_MLP(512, 512, 300, linear_layer=False, tag='encoders.0'),
                    IO.MaxOut_MLP(512, 1024, 4096, 512, False, tag='encoders.1')], _RefFusion([512, 512], 512, 16),
                   IO.Linear(512, 23))
-    _randomize_bn(ref, 3)
+    randomize_bn(ref, 3)
     mine.load_state_dict(ref.state_dict(), strict=True)
     mine, ref = mine.cuda().train(), ref.double().train()
     B, lr, wd = 128, 1e-3, 1e-2
@@ -480,7 +465,7 @@ def test_imdb_lrtf_train_step_against_oracle():
         IO.MASKS.clear()
     torch.cuda.synchronize()
     step.opt.check_finite()
-    _check_params(mine, ref, names, lr, 'imdb_lrtf')
+    check_adam_params(mine, ref, lr, 'imdb_lrtf', names)
     sd, sd_r = mine.state_dict(), ref.state_dict()
     for k in sd:
         if 'running_' in k:

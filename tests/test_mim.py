@@ -20,7 +20,7 @@ from dynmm_amd import experts as E
 from dynmm_amd import lib as L
 from dynmm_amd import ops_mlp as M
 from dynmm_amd.nn import imdb as I
-from tests.test_gru import _rel
+from tests.parity import check_adam_params, compare_to_float64, randomize_bn, rel as _rel
 
 FWD, BWD = 1e-5, 2e-5                         # test_seq_kernels.py: LN_FWD, LN_BWD
 
@@ -76,20 +76,6 @@ def _ref(shape, init):
         c = _case(shape, init)
         _REF[key] = (c, _run(mim_ref, c, torch.float64), _run(mim_ref, c, torch.float32))
     return _REF[key]
-
-
-def _compare(tag, got, ref64, ref32):
-    bad = []
-    for k in ref64:
-        project = FWD if k == 'out' else BWD
-        assert tuple(got[k].shape) == tuple(ref64[k].shape), (tag, k)
-        err, yard = _rel(got[k], ref64[k]), _rel(ref32[k], ref64[k])
-        bar = max(project, 4.0 * yard)
-        finite = bool(torch.isfinite(got[k]).all())
-        print(f'FIG {tag} {k} kernel={err:.3e} f32={yard:.3e} bar={bar:.3e}' + (' RAISED' if err >= project else ''))
-        if not (finite and err < bar):
-            bad.append((k, err, yard, bar, finite))
-    assert not bad, (tag, bad)
 
 
 def _ids(s):
@@ -202,7 +188,7 @@ def test_workspaces_stay_under_a_quarter_of_the_intermediate():
 @pytest.mark.parametrize('shape', SHAPES, ids=_ids)
 def test_mim_against_float64(shape, init):
     c, r64, r32 = _ref(shape, init)
-    _compare(f'{_ids(shape)} {init}', _run(M.mim, c, torch.float32, 'cuda'), r64, r32)
+    compare_to_float64(f'{_ids(shape)} {init}', _run(M.mim, c, torch.float32, 'cuda'), r64, r32, ('out',), FWD, BWD)
 
 
 @pytest.mark.gpu
@@ -220,7 +206,7 @@ def test_mim_at_the_reference_geometry():
     torch.cuda.empty_cache()
     r64 = _run(mim_ref, c, torch.float64, 'cuda')
     torch.cuda.empty_cache()
-    _compare(f'{_ids(FULL)} unit', got, r64, r32)
+    compare_to_float64(f'{_ids(FULL)} unit', got, r64, r32, ('out',), FWD, BWD)
 
 
 @pytest.mark.gpu
@@ -322,12 +308,11 @@ def test_imdb_mim_train_step_against_oracle():
     """Two steps at batch 128 with output_dim 32: BatchNorm in training mode, dropout p = 0.3 with injected keep flags."""
     from dynmm_amd import ops_seq as S
     from tests import imdb_oracle as IO
-    from tests.test_experts import _check_params, _randomize_bn
     torch.manual_seed(5)
     mine, _ = E.imdb_mm_mim(output_dim=32)
     ref = IO.MMDL([IO.MaxOut_MLP(512, 512, 300, linear_layer=False, tag='encoders.0'),
                    IO.MaxOut_MLP(512, 1024, 4096, 512, False, tag='encoders.1')], _RefFusion(512, 512, 32), IO.Linear(32, 23))
-    _randomize_bn(ref, 3)
+    randomize_bn(ref, 3)
     mine.load_state_dict(ref.state_dict(), strict=True)
     mine, ref = mine.cuda().train(), ref.double().train()
     B, lr, wd = 128, 1e-3, 1e-2
@@ -368,7 +353,7 @@ def test_imdb_mim_train_step_against_oracle():
         IO.MASKS.clear()
     torch.cuda.synchronize()
     step.opt.check_finite()
-    _check_params(mine, ref, names, lr, 'imdb_mim')
+    check_adam_params(mine, ref, lr, 'imdb_mim', names)
     sd, sd_r = mine.state_dict(), ref.state_dict()
     for k in sd:
         if 'running_' in k:

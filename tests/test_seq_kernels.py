@@ -53,15 +53,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.parity import rel as _rel
+
 EPS = 1e-5
 LN_FWD, LN_BWD = 1e-5, 2e-5                  # test_affect.py: LayerNorm and attention
 FFN_FWD, FFN_BWD = 2e-5, 1e-4                # test_affect.py: the fused feed-forward block (output, data gradient)
 CLIP_REL = 1.2e-7
-
-
-def _rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
 
 
 class _Figures:
