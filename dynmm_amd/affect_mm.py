@@ -7,7 +7,8 @@ lf_tran.pt and b2_lf_tran.pt (the name dynmm_amd.affect --model v2 reads) under 
 validation and the test split with single_test (Accuracy, Loss, Corr).  The other switches are refused: the GRU fusions
 (--fusion 0, 1, 5) and the early-fusion transformer (--fusion 2, ef_tran: Transformer(409, 300) + MLP(300, 128, 1)) run on the
 HIP path at the module level (experts.affect_mm_gru, affect_mm_lrtf, affect_mm_ef_tran; file_names gives their file names) but
-are not wired to the command line yet; MULT (--fusion 4) has no HIP kernels.  Data as dynmm_amd.affect."""
+are not wired to the command line yet, and so is MULT (--fusion 4: experts.affect_mm_mult, nn.mult.MULTModel).  Data as
+dynmm_amd.affect."""
 import argparse
 import os
 

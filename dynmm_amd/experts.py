@@ -25,6 +25,7 @@ File contract (state_dicts, read with strict=True by imdb.load_pretrained and af
   affect_mm_lrtf()         lrtf.pt                                             yet)
   imdb_mm_mim()            best_mim.pt                                        (builder: --fuse 3 is not wired yet)
   affect_mm_ef_tran()      ef_tran.pt                                         (builder: --fusion 2 is not wired yet)
+  affect_mm_mult()         mult.pt                                            (builder: --fusion 4 is not wired yet)
 The b1_ / b2_ copies are the names affect_dyn.py:211 (`--model v2`) reads, which a reference user makes by renaming.
 """
 import copy
@@ -41,6 +42,7 @@ from . import ops_mlp as M
 from . import ops_seq as S
 from .nn import affect as A
 from .nn import imdb as I
+from .nn import mult as MU
 
 PATIENCE = 7                 # Supervised_Learning.train: `if early_stop and patience > 7: break`
 
@@ -124,8 +126,8 @@ def affect_uni(mod, enc='transformer', hidden_dim1=0, hidden_dim2=0, clf=False):
 
 def affect_mm(fusion):
     """affect_mm.py: the MMDL of `--fusion` (3: late-fusion transformers, DynMMNetV2's branch2).  The other switches are refused;
-    the models of 0 / 1 (affect_mm_gru), 2 (affect_mm_ef_tran) and 5 (affect_mm_lrtf) are built by their own functions, 4 (MULT)
-    has no HIP kernels."""
+    the models of 0 / 1 (affect_mm_gru), 2 (affect_mm_ef_tran), 4 (affect_mm_mult) and 5 (affect_mm_lrtf) are built by their own
+    functions."""
     if fusion == 3:
         return A.late_fusion_transformer()
     if fusion in (0, 1):
@@ -134,7 +136,8 @@ def affect_mm(fusion):
     if fusion == 5:
         raise _not_wired(*_FUSION_5)
     if fusion == 4:
-        raise NotImplementedError('affect_mm --fusion 4 (mult): MULTModel has no HIP kernels')
+        raise _not_wired('affect_mm --fusion 4 (mult)', 'MULT model (MULTModel(3, [35, 74, 300]))',
+                         'dynmm_amd.nn.mult.MULTModel, experts.affect_mm_mult')
     if fusion == 2:
         raise _not_wired('affect_mm --fusion 2 (ef_tran)', 'early-fusion Transformer(409, 300) model',
                          'dynmm_amd.nn.affect.early_fusion_transformer, experts.affect_mm_ef_tran')
@@ -179,6 +182,13 @@ def affect_mm_ef_tran():
     return A.early_fusion_transformer()
 
 
+def affect_mm_mult():
+    """affect_mm.py `--fusion 4` (mult: Identity encoders, MULTModel(3, [35, 74, 300], HParams) as the fusion, Identity head;
+    mult.pt through affect_mm.file_names(dir, 4)).  Nine cross-modal transformers (embed_dim 40, 10 heads: head dimension 4) and
+    three memory transformers (120 channels: head dimension 12), all pre-norm with the future mask: ops_seq.cross_attention."""
+    return MU.mult_model()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # train step
 # ---------------------------------------------------------------------------------------------------------------------
@@ -211,7 +221,7 @@ class ExpertTrainStep(engine.FlatAdamWStep):
     def __init__(self, model, objective, lr, weight_decay, clip_val=8.0, use_graph=False):
         if objective not in M.HEAD_LOSSES:
             raise ValueError(f'objective must be one of {sorted(M.HEAD_LOSSES)}, got {objective!r}')
-        depth = [len(m.layers) for m in model.modules() if isinstance(m, nn.TransformerEncoder)]
+        depth = [len(m.layers) for m in model.modules() if isinstance(m, (nn.TransformerEncoder, MU.TransformerEncoder))]
         self.has_bn = any(isinstance(m, nn.BatchNorm1d) for m in model.modules())
         if use_graph and self.has_bn:
             raise ValueError('ExpertTrainStep(use_graph=True): only for models without BatchNorm (the transformer experts)')

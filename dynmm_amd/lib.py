@@ -21,6 +21,7 @@ c_f = C.c_void_p       # device pointers travel as void* (tensor.data_ptr() or N
 c_i = C.c_int
 c_fl = C.c_float
 c_sz = C.c_size_t
+c_ll = C.c_longlong
 
 
 class ConvGeom(C.Structure):
@@ -204,6 +205,14 @@ SIGNATURES = {
     'dynmm_attn_supported': (c_i, [c_i, c_i, c_i]),
     'dynmm_attn_fwd': (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, _DP, c_f]),
     'dynmm_attn_bwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, _DP, c_f]),
+    'dynmm_xattn_supported': (c_i, [c_i] * 4),
+    'dynmm_xattn_fwd': (c_i, [c_f] * 3 + [c_ll] * 3 + [c_f, c_f] + [c_i] * 6 + [_DP, c_f]),
+    'dynmm_xattn_bwd': (c_i, [c_f] * 4 + [c_ll] * 3 + [c_f] * 4 + [c_ll] * 3 + [c_i] * 6 + [_DP, c_f]),
+    'dynmm_posembed_fwd': (c_i, [c_f] * 4 + [c_i] * 3 + [c_fl, _DP, _DP, c_f]),
+    'dynmm_posembed_bwd': (c_i, [c_f] * 3 + [c_i] * 3 + [c_fl, _DP, _DP, c_f]),
+    'dynmm_prenorm_fwd': (c_i, [c_f] * 8 + [c_i] * 3 + [c_fl, _DP, c_f]),
+    'dynmm_prenorm_bwd_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
+    'dynmm_prenorm_bwd': (c_i, [c_f] * 10 + [c_i] * 3 + [_DP, c_i, c_f, c_sz, c_f]),
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 

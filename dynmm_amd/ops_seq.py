@@ -2,7 +2,8 @@
 
 Activations are [B, D, T] fp32 (the layout the reference feeds its Conv1d after `x.permute([0, 2, 1])`); every Linear
 / Conv1d(k=1) is `linear_bdt` = the implicit-GEMM MFMA convolution of ops.conv2d with H = 1, W = T.  The kernels
-added for this path live in csrc/seq.hip (attention for head dimensions above 32: csrc/attn.hip).  As everywhere in dynmm_amd there is no CPU / eager fallback.
+added for this path live in csrc/seq.hip (attention for head dimensions above 32: csrc/attn.hip; MULT's masked cross-modal
+attention, embedding and pre-norm plumbing: csrc/xattn.hip).  As everywhere in dynmm_amd there is no CPU / eager fallback.
 """
 import ctypes as C
 import itertools
@@ -535,6 +536,240 @@ def attention(qkv, heads, drop=None):
     the kernel and the launch they always had), mha_wide above it (Transformer(409, 300): dh = 60)."""
     dh = qkv.shape[1] // 3 // heads
     return mha_core(qkv, heads, drop) if dh <= MHA_CORE_MAX_DH else mha_wide(qkv, heads, drop)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# MULT (MultiBench fusions.mult.MULTModel): masked cross-modal attention, the embedding and the pre-norm plumbing, csrc/xattn.hip
+# ---------------------------------------------------------------------------------------------------------------
+XATTN_MAX_DH, XATTN_MAX_T = 32, 64       # csrc/xattn.hip: kXaMaxDh, kXaMaxT
+
+
+def _bdt_view(t, name):
+    """t [B, D, T] fp32 on the device whose samples are contiguous [D, T] blocks (a contiguous tensor or a channel slice of
+    one: the packed q | k | v of an in_proj); anything else is copied."""
+    _chk(t, name)
+    if t.dim() != 3:
+        raise L.DynmmHipError(f'cross_attention: {name} must be [B, D, T], got {tuple(t.shape)}')
+    B, D, T = t.shape
+    if t.stride(2) == 1 and t.stride(1) == T and (B == 1 or t.stride(0) >= D * T):
+        return t
+    return t.contiguous()
+
+
+def _bstride(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2]
+
+
+def _xattn_fwd(q, k, v, heads, causal, drop):
+    B, D, Tq = q.shape
+    Tk = k.shape[2]
+    if tuple(k.shape) != (B, D, Tk) or tuple(v.shape) != (B, D, Tk):
+        raise L.DynmmHipError(f'cross_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree')
+    out = torch.empty((B, D, Tq), device=q.device, dtype=torch.float32)
+    probs = torch.empty((B * heads, Tq, Tk), device=q.device, dtype=torch.float32)
+    L.check(_lib().dynmm_xattn_fwd(_p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(out), _p(probs), B, D, Tq, Tk,
+                                   heads, causal, _drop_arg(drop), _stream()), 'xattn_fwd')
+    return out, probs
+
+
+def _xattn_bwd(g, q, k, v, probs, dq, dk, dv, heads, causal, drop):
+    B, D, Tq = q.shape
+    L.check(_lib().dynmm_xattn_bwd(_p(g), _p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(probs), _p(dq), _p(dk),
+                                   _p(dv), _bstride(dq), _bstride(dk), _bstride(dv), B, D, Tq, k.shape[2], heads, causal,
+                                   _drop_arg(drop), _stream()), 'xattn_bwd')
+
+
+class _CrossAttention(Function):
+    """out [B, D, Tq] of (q [B, D, Tq], k, v [B, D, Tk]); saves its inputs and the probabilities before dropout."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, causal, drop=None):
+        q, k, v = _bdt_view(q, 'q'), _bdt_view(k, 'k'), _bdt_view(v, 'v')
+        ctx.drop, ctx.heads, ctx.causal = drop, heads, int(bool(causal))
+        out, probs = _xattn_fwd(q, k, v, heads, ctx.causal, drop)
+        ctx.save_for_backward(q, k, v, probs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, probs = ctx.saved_tensors
+        g = _chk(g, 'grad')
+        dq, dk, dv = (torch.empty(t.shape, device=g.device, dtype=torch.float32) for t in (q, k, v))
+        _xattn_bwd(g, q, k, v, probs, dq, dk, dv, ctx.heads, ctx.causal, ctx.drop)
+        return dq, dk, dv, None, None, None
+
+
+class _PackedAttention(Function):
+    """_CrossAttention on the channel thirds q | k | v of one qkv [B, 3D, T]; the gradient is one [B, 3D, T] tensor."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, causal, drop=None):
+        qkv = _chk(qkv, 'qkv')
+        D = qkv.shape[1] // 3
+        ctx.drop, ctx.heads, ctx.causal = drop, heads, int(bool(causal))
+        out, probs = _xattn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], heads, ctx.causal, drop)
+        ctx.save_for_backward(qkv, probs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, probs = ctx.saved_tensors
+        g = _chk(g, 'grad')
+        D = qkv.shape[1] // 3
+        dqkv = torch.empty_like(qkv)
+        _xattn_bwd(g, qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], probs, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
+                   ctx.heads, ctx.causal, ctx.drop)
+        return dqkv, None, None, None
+
+
+def _xattn_drop(drop, B, heads, Tq, Tk, device):
+    if drop is None or not drop[0] > 0:
+        return None
+    return Drop(drop[0], drop[1], drop[2], (B * heads, Tq, Tk), device)
+
+
+def cross_attention(q, k, v, heads, causal, drop=None):
+    """dropout(softmax(q k^T / sqrt(dh) + mask)) v per head for q [B, D, Tq], k and v [B, D, Tk] -> [B, D, Tq].  causal: key j is
+    visible to query i iff j <= i + |Tk - Tq| (MULT's future mask, torch.triu(-inf, 1 + |Tk - Tq|)).  q, k, v may be channel
+    slices of one packed [B, 3D, T] tensor (no copy; `packed_attention` also returns their gradient as one tensor).
+    drop = (p, site, name) or None: dropout on the [B*heads, Tq, Tk] probabilities.  Head dimensions up to 32, lengths up to 64
+    (csrc/xattn.hip)."""
+    return _CrossAttention.apply(q, k, v, heads, causal, _xattn_drop(drop, q.shape[0], heads, q.shape[2], k.shape[2], q.device))
+
+
+def packed_attention(qkv, heads, causal, drop=None):
+    """cross_attention on qkv [B, 3D, T] (q | k | v along channels, an in_proj's output): masked self-attention."""
+    B, _, T = qkv.shape
+    return _PackedAttention.apply(qkv, heads, causal, _xattn_drop(drop, B, heads, T, T, qkv.device))
+
+
+class _PosEmbed(Function):
+    """(y1[, y2]) = dropout_s(scale x + pos) for one or two sites."""
+
+    @staticmethod
+    def forward(ctx, x, pos, scale, drop1, drop2, two):
+        x = _chk(x, 'x')
+        B, E, T = x.shape
+        y1 = torch.empty_like(x)
+        y2 = torch.empty_like(x) if two else None
+        L.check(_lib().dynmm_posembed_fwd(_p(x), _p(pos), _p(y1), _p(y2), B, E, T, float(scale), _drop_arg(drop1),
+                                          _drop_arg(drop2), _stream()), 'posembed_fwd')
+        ctx.drops, ctx.scale, ctx.two = (drop1, drop2), float(scale), two
+        ctx.set_materialize_grads(False)
+        return (y1, y2) if two else y1
+
+    @staticmethod
+    def backward(ctx, g1, g2=None):
+        d1, d2 = ctx.drops
+        if g1 is None:
+            g1, g2, d1, d2 = g2, None, d2, None
+        if g1 is None:
+            return None, None, None, None, None, None
+        g1, g2 = _chk(g1, 'grad'), _chk(g2, 'grad')
+        B, E, T = g1.shape
+        dx = torch.empty_like(g1)
+        L.check(_lib().dynmm_posembed_bwd(_p(g1), _p(g2), _p(dx), B, E, T, ctx.scale, _drop_arg(d1),
+                                          _drop_arg(d2) if g2 is not None else None, _stream()), 'posembed_bwd')
+        return dx, None, None, None, None, None
+
+
+def pos_embed(x, pos, scale, drop=None, drop2=None):
+    """MULT's embedding of x [B, E, T]: dropout(scale x + pos), pos [E, T] the sinusoid table of positions 1..T, left out at the
+    time steps whose x[b, 0, t] is exactly 0 (padding).  drop / drop2 = (p, site, name): with drop2 the launch returns two outputs
+    with dropout decisions of their own (the key and the value embedding of one source)."""
+    pos = _operand('pos_embed', pos, 'pos', (x.shape[1], x.shape[2]))
+    mk = lambda d: Drop(d[0], d[1], d[2], x.shape, x.device) if d is not None and d[0] > 0 else None      # noqa: E731
+    return _PosEmbed.apply(x, pos, scale, mk(drop), mk(drop2), drop2 is not None)
+
+
+class _PreNorm(Function):
+    """(sum, y) = (res + dropout(x), LayerNorm(sum)); x None: y alone (sum = res).  direct: the parameter gradients may take the
+    in-place gradient protocol (the LayerNorm is applied ONCE per step; a LayerNorm shared by several inputs returns its
+    gradients to autograd, which sums them)."""
+
+    @staticmethod
+    def forward(ctx, res, x, gamma, beta, eps, drop, direct):
+        lib = _lib()
+        res, x, gamma, beta = _chk(res, 'res'), _chk(x, 'x'), _chk(gamma, 'gamma'), _chk(beta, 'beta')
+        B, D, T = res.shape
+        y = torch.empty_like(res)
+        s = torch.empty_like(res) if x is not None else None
+        mean = torch.empty(B * T, device=res.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+        L.check(lib.dynmm_prenorm_fwd(_p(x), _p(res), _p(gamma), _p(beta), _p(s), _p(y), _p(mean), _p(rstd), B, D, T, float(eps),
+                                      _drop_arg(drop), _stream()), 'prenorm_fwd')
+        ctx.drop, ctx.direct, ctx.has_x = drop, direct, x is not None
+        ctx.save_for_backward(s if x is not None else res, gamma, mean, rstd)
+        ctx.g_param, ctx.b_param = gamma, beta
+        ctx.set_materialize_grads(False)
+        return (s, y) if x is not None else y
+
+    @staticmethod
+    def backward(ctx, *grads):
+        lib = _lib()
+        s, gamma, mean, rstd = ctx.saved_tensors
+        gs, gy = grads if ctx.has_x else (None, grads[0])
+        B, D, T = s.shape
+        if gy is None:
+            if gs is None:
+                return (None,) * 7
+            gy = torch.zeros_like(s)               # only the sum was used downstream (no model of this project does that)
+        gy, gs = _chk(gy, 'grad'), _chk(gs, 'grad')
+        need_res, need_x = ctx.needs_input_grad[0], ctx.has_x and ctx.needs_input_grad[1]
+        dropping = ctx.drop is not None and ctx.drop.p > 0
+        dres = torch.empty_like(s) if (need_res or (need_x and not dropping)) else None
+        dx = torch.empty_like(s) if (need_x and dropping) else None
+        dg = dg_ret = db = db_ret = ws = None
+        nb = 0
+        acc = 0
+        if ctx.needs_input_grad[2]:
+            if ctx.direct or (ops._direct_ok(ctx.g_param) and ops._direct_ok(ctx.b_param)):
+                # in place: a LayerNorm applied once per step overwrites its gradient, a shared one ADDS to it (.grad's own
+                # meaning; the step's gradient buffer starts at zero) — no accumulation pass by autograd
+                dg, dg_ret = _grad_dst(ctx.g_param)
+                db, db_ret = _grad_dst(ctx.b_param)
+                acc = int(not ctx.direct and dg_ret is None and db_ret is None)
+            else:
+                dg = dg_ret = torch.empty_like(gamma)
+                db = db_ret = torch.empty_like(gamma)
+            nb = lib.dynmm_prenorm_bwd_workspace_bytes(B, D, T)
+            ws = torch.empty(nb // 4, device=s.device, dtype=torch.float32)
+        L.check(lib.dynmm_prenorm_bwd(_p(gy), _p(gs), _p(s), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dg), _p(db), B,
+                                      D, T, _drop_arg(ctx.drop), acc, _p(ws), nb, _stream()), 'prenorm_bwd')
+        _grads_enqueued()
+        return (dres if need_res else None), ((dx if dropping else dres) if need_x else None), dg_ret, db_ret, None, None, None
+
+
+def prenorm_bdt(res, gamma, beta, eps=1e-5, x=None, drop=None, shared=False):
+    """The plumbing of a pre-norm layer, one launch: with x, (res + dropout(x), LayerNorm of that sum) — both are returned, the sum
+    is the next residual input and the normalisation feeds the next block; without x, LayerNorm(res) alone.  drop = (p, site,
+    name) or None.  shared: this LayerNorm's parameters are applied to several inputs in one step (MULT's LN0 on query, key and
+    value): inside a training step their gradients are ADDED to the parameter's gradient in place instead of overwriting it,
+    otherwise they go back to autograd, which sums them."""
+    d = Drop(drop[0], drop[1], drop[2], x.shape, x.device) if x is not None and drop is not None and drop[0] > 0 else None
+    return _PreNorm.apply(res, x, gamma, beta, eps, d, not shared)
+
+
+class _ResidualAdd(Function):
+    """res + x, [B, D, ...] (csrc/xattn.hip's pre-norm kernel without its LayerNorm)."""
+
+    @staticmethod
+    def forward(ctx, res, x):
+        res, x = _chk(res, 'res'), _chk(x, 'x')
+        B, D = res.shape[0], res.shape[1]
+        s = torch.empty_like(res)
+        L.check(_lib().dynmm_prenorm_fwd(_p(x), _p(res), None, None, _p(s), None, None, None, B, D, res.numel() // (B * D), 0.0,
+                                         None, _stream()), 'prenorm_fwd')
+        return s
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, g
+
+
+def residual_add(res, x):
+    """res + x as a HIP launch (the head of MULT: proj2(...) + z)."""
+    return _ResidualAdd.apply(res, x)
 
 
 class _MoEBlend(Function):

@@ -792,6 +792,48 @@ int dynmm_attn_fwd(const float* qkv, float* out, float* probs, int B, int D, int
 int dynmm_attn_bwd(const float* g, const float* qkv, const float* probs, float* dqkv, int B, int D, int T, int heads,
                    const dynmm_dropout* drop, void* stream);
 
+/* ---- MULT (MultiBench fusions.mult.MULTModel, affect_mm.py --fusion 4), csrc/xattn.hip ----
+ * Masked cross-modal attention: q [B, D, Tq], k and v [B, D, Tk], each with a batch stride of its own in floats (three tensors or
+ * the slices of a packed [B, 3D, T] both work; inside a sample the channel stride is the sequence length), out [B, D, Tq],
+ * probs [B*heads, Tq, Tk] = the probabilities BEFORE dropout (row maximum subtracted, rows sum to 1, masked entries exactly 0).
+ * q is scaled by 1/sqrt(dh) before the product.  causal != 0: key j is visible to query i iff j <= i + |Tk - Tq|
+ * (torch.triu(-inf, 1 + |Tk - Tq|)); causal == 0: no mask.  drop (optional): the dropout site of the probabilities, indexed as
+ * dynmm_mha_drop_fwd indexes it (flat query row, chunks of 8 keys): injected flags are the flat [B*heads, Tq, Tk] bytes, and at
+ * Tq == Tk the generator draws dynmm_mha_drop_fwd's decisions; the backward regenerates them.  bwd: g [B, D, Tq] -> dq, dk, dv
+ * (overwritten) with batch strides of their own.  1 <= D/heads <= 32 and 1 <= Tq, Tk <= 64, any B and heads
+ * (dynmm_xattn_supported = 1); outside that DYNMM_EUNSUPPORTED, a malformed call (D % heads != 0, a batch stride below D * T)
+ * DYNMM_EINVAL, nothing written in either case.  One wave per (sample, head); fp32 in, fp32 accumulate; no atomics, no workspace,
+ * no host synchronisation: equal inputs give equal bits, and both calls can be captured. */
+int dynmm_xattn_supported(int D, int Tq, int Tk, int heads);
+int dynmm_xattn_fwd(const float* q, const float* k, const float* v, long long q_bstride, long long k_bstride,
+                    long long v_bstride, float* out, float* probs, int B, int D, int Tq, int Tk, int heads, int causal,
+                    const dynmm_dropout* drop, void* stream);
+int dynmm_xattn_bwd(const float* g, const float* q, const float* k, const float* v, long long q_bstride, long long k_bstride,
+                    long long v_bstride, const float* probs, float* dq, float* dk, float* dv, long long dq_bstride,
+                    long long dk_bstride, long long dv_bstride, int B, int D, int Tq, int Tk, int heads, int causal,
+                    const dynmm_dropout* drop, void* stream);
+/* The embedding of MULT's TransformerEncoder: y = dropout(scale * x + pos) for x [B, E, T]; pos [E, T] (the sinusoid table of the
+ * positions 1..T) is left out where x[b, 0, t] == 0.0 exactly (a padded time step).  y2 / drop2 (optional): a second output with
+ * dropout decisions of its own (the key and the value embedding of one source).  bwd: dx = scale * (keep1 * g1 + keep2 * g2)
+ * (g2 optional); the positional term carries no gradient.  Dropout sites are [B, E, T] sites (eight channels per generator call,
+ * injected flags in the tensor's flat layout). */
+int dynmm_posembed_fwd(const float* x, const float* pos, float* y1, float* y2, int B, int E, int T, float scale,
+                       const dynmm_dropout* drop1, const dynmm_dropout* drop2, void* stream);
+int dynmm_posembed_bwd(const float* g1, const float* g2, float* dx, int B, int E, int T, float scale,
+                       const dynmm_dropout* drop1, const dynmm_dropout* drop2, void* stream);
+/* Pre-norm plumbing: sum = res + dropout(x) (x NULL: sum = res, nothing dropped) and y = LayerNorm over D of sum, [B, D, T], in one
+ * launch; sum (optional when gamma is given) and y are both written; gamma NULL: the residual sum alone (x and sum required).
+ * bwd: gy = the gradient of y, gs (optional) = the gradient that reaches sum directly; d = LayerNorm backward of gy at sum + gs;
+ * dres (optional) = d, dx (optional) = d * keep; dgamma and dbeta (both or neither; then the workspace of
+ * dynmm_prenorm_bwd_workspace_bytes is required, else DYNMM_EWORKSPACE) are OVERWRITTEN, or with accumulate != 0 ADDED TO (a
+ * LayerNorm applied to several inputs in one step; the calls of one stream add in order), summed in a fixed order.  D <= 1024. */
+int dynmm_prenorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* sum, float* y,
+                      float* mean, float* rstd, int B, int D, int T, float eps, const dynmm_dropout* drop, void* stream);
+size_t dynmm_prenorm_bwd_workspace_bytes(int B, int D, int T);
+int dynmm_prenorm_bwd(const float* gy, const float* gs, const float* sum, const float* gamma, const float* mean,
+                      const float* rstd, float* dx, float* dres, float* dgamma, float* dbeta, int B, int D, int T,
+                      const dynmm_dropout* drop, int accumulate, float* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- NYUv2 input pipeline (FusionDynMM/src/preprocessing.py), csrc/rgbd_aug.hip ---- */
 /* One batch of network inputs from decoded samples kept on the device: rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit,
  * label [S,H0,W0] uint8.  params [N,8] int32 per output sample: {stored index, th, tw, mode, ci, cj, flip, 0}: the stored sample
