@@ -198,6 +198,38 @@ __global__ void __launch_bounds__(256) se_coeff_bwd_kernel(
                dz_d + (size_t)n * C, dh_d + (size_t)n * Hd, dsd + (size_t)n * C, C, Hd, act);
 }
 
+// One excitation MLP on one pooled tensor (model_utils.py:36-51 stand-alone: the one-modality networks; se_scale.hip holds the
+// feature-map passes).  g = sigmoid(W2 act(W1 s + b1) + b2); params = W1 b1 W2 b2.
+struct Se1Params { const float* p[4]; };
+
+__global__ void __launch_bounds__(256) se1_coeff_fwd_kernel(const float* __restrict__ s, Se1Params P, float* __restrict__ h,
+                                                            float* __restrict__ g, int C, int act) {
+    __shared__ float s_lds[kMaxC];
+    __shared__ float h_lds[kMaxHid];
+    const int n = blockIdx.x;
+    const int Hd = C / 16;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) s_lds[c] = s[(size_t)n * C + c];
+    __syncthreads();
+    se_mlp_fwd(s_lds, P.p[0], P.p[1], P.p[2], P.p[3], h_lds, h + (size_t)n * Hd, g + (size_t)n * C, C, Hd, act);
+}
+
+// scratch layout: dz [N][C] | dh [N][Hd]
+__global__ void __launch_bounds__(256) se1_coeff_bwd_kernel(const float* __restrict__ dg, Se1Params P,
+                                                            const float* __restrict__ h, const float* __restrict__ g,
+                                                            float* __restrict__ ws, float* __restrict__ ds, int N, int C,
+                                                            int act) {
+    __shared__ float dg_lds[kMaxC];
+    __shared__ float dz_lds[kMaxC];
+    __shared__ float dh_lds[kMaxHid];
+    const int n = blockIdx.x;
+    const int Hd = C / 16;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) dg_lds[c] = dg[(size_t)n * C + c];
+    __syncthreads();
+    float* const dz = ws, * const dh = dz + (size_t)N * C;
+    se_mlp_bwd(dg_lds, h + (size_t)n * Hd, g + (size_t)n * C, P.p[0], P.p[2], dz_lds, dh_lds, dz + (size_t)n * C,
+               dh + (size_t)n * Hd, ds + (size_t)n * C, C, Hd, act);
+}
+
 // ------------------------------------------------------------------------------------------------
 // gate head (single workgroup; N samples looped by the threads)
 // ------------------------------------------------------------------------------------------------
@@ -575,6 +607,52 @@ extern "C" int dynmm_se_coeff_bwd(const float* da, const float* db, const float*
                                   int dwc_stride, float* workspace, int N, int C, int use_se, void* stream) {
     return dynmm_se_coeff_bwd_act(da, db, sr, sd, params, wc, wc_stride, hr, hd, gr, gd, dparams, dsr, dsd, dwc, dwc_stride,
                                   workspace, N, C, use_se, DYNMM_ACT_RELU, stream);
+}
+
+static int se1_check(int N, int C, int act) {
+    if (N <= 0 || C <= 0 || C > kMaxC || !act_is_known(act)) return DYNMM_EINVAL;
+    if (C % 16 != 0 || C / 16 > kMaxHid) return DYNMM_EUNSUPPORTED;
+    return DYNMM_OK;
+}
+
+extern "C" int dynmm_se1_coeff_fwd(const float* s, const float* const* params, float* h, float* g, int N, int C, int act,
+                                   void* stream) {
+    (void)hipGetLastError();   // drop stale errors left by other users of the runtime
+    if (!s || !params || !h || !g) return DYNMM_EINVAL;
+    if (const int rc = se1_check(N, C, act)) return rc;
+    Se1Params P{};
+    for (int i = 0; i < 4; ++i) {
+        if (!params[i]) return DYNMM_EINVAL;
+        P.p[i] = params[i];
+    }
+    hipLaunchKernelGGL(se1_coeff_fwd_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, s, P, h, g, C, act);
+    DYNMM_LAUNCH_CHECK();
+    return DYNMM_OK;
+}
+
+extern "C" size_t dynmm_se1_coeff_bwd_workspace_bytes(int N, int C) {
+    return sizeof(float) * (size_t)N * (size_t)(C + C / 16);
+}
+
+extern "C" int dynmm_se1_coeff_bwd(const float* dg, const float* s, const float* const* params, const float* h,
+                                   const float* g, float* const* dparams, float* ds, float* workspace, int N, int C, int act,
+                                   void* stream) {
+    (void)hipGetLastError();
+    if (!dg || !s || !params || !h || !g || !dparams || !ds) return DYNMM_EINVAL;
+    if (!workspace) return DYNMM_EWORKSPACE;
+    if (const int rc = se1_check(N, C, act)) return rc;
+    Se1Params P{};
+    for (int i = 0; i < 4; ++i) {
+        if (!params[i] || !dparams[i]) return DYNMM_EINVAL;
+        P.p[i] = params[i];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(se1_coeff_bwd_kernel, dim3(N), dim3(256), 0, st, dg, P, h, g, workspace, ds, N, C, act);
+    DYNMM_LAUNCH_CHECK();
+    const int Hd = C / 16;
+    MlpGradJobs jobs{};
+    jobs.j[0] = MlpGradJob{s, h, workspace, workspace + (size_t)N * C, dparams[0], dparams[1], dparams[2], dparams[3], 0, nullptr};
+    return launch_mlp_param_grad(jobs, 1, N, C, Hd, act, st);      // samples summed in ascending order: no float atomics
 }
 
 extern "C" int dynmm_gate_head_fwd(const float* pooled, const float* fc, float* weight, float* wcum,

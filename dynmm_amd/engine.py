@@ -563,7 +563,7 @@ class InferStep:
     def _key(self, rgb, depth):
         m = self.model
         bo = getattr(m, 'branch_override', None)
-        if getattr(m, 'ini_stage', False):
+        if getattr(m, 'ini_stage', False) and not getattr(m, 'gate_free', False):
             bo = ('ini',) + tuple(int(v) for v in m.ini_branches)
         return (tuple(rgb.shape), tuple(depth.shape), bool(getattr(m, 'baseline', False)), bool(getattr(m, 'hard_gate', False)),
                 float(getattr(m, 'temp', 0.0)), bool(getattr(m, 'compact', False)), bool(getattr(m, 'dual_stream', False)),
@@ -597,8 +597,12 @@ class InferStep:
     def __call__(self, rgb, depth, return_weight=False):
         m = self.model
         gated = hasattr(m, 'forward_front')
-        host_decisions = (getattr(m, 'ini_stage', False) and getattr(m, 'ini_branches', None) is None) or \
-            (not gated and (hasattr(m, 'hard_gate') or hasattr(m, 'block_rule')))
+        # (gate_free: a network without any gate — ESANetOneModality — stays one graph although evaluate() / train.run / eval.run
+        #  leave `hard_gate`, `ini_stage`, `baseline` attributes on whatever model they are given)
+        gate_free = not gated and getattr(m, 'gate_free', False)
+        host_decisions = not gate_free and (
+            (getattr(m, 'ini_stage', False) and getattr(m, 'ini_branches', None) is None) or
+            (not gated and (hasattr(m, 'hard_gate') or hasattr(m, 'block_rule'))))
         if m.training or host_decisions:
             return self._eager(rgb, depth, return_weight)
         stamp = self._weights_stamp()

@@ -12,7 +12,7 @@ import torch
 from . import engine
 from .data import SyntheticRGBD, nyuv2_split
 from .src.args import ArgumentParserRGBDSegmentation
-from .src.build_model import build_model
+from .src.build_model import build_for_args
 
 
 def set_seed(seed):
@@ -67,7 +67,7 @@ def main(argv=None):
     args.pretrained_on_imagenet = False
     if args.dataset_dir is not None and args.dataset not in ('nyuv2', 'synthetic'):
         raise NotImplementedError(f'--dataset {args.dataset}: only nyuv2 (and synthetic) have a reader on the HIP path')
-    model, device = build_model(args, n_classes=40)
+    model, device = build_for_args(args, n_classes=40)
     if args.ckpt_path:
         ckpt = torch.load(args.ckpt_path, map_location=device)
         model.load_state_dict(ckpt['state_dict'])               # strict, eval.py:60-61

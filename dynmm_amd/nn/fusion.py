@@ -1,5 +1,6 @@
 """SE fusion containers (rgb_depth_fusion.py:13-26, model_utils.py:36-51).  The arithmetic (GAP,
-excitation MLPs, channel scaling, modality sum AND the gate blend) runs in ops.se_fuse_blend."""
+excitation MLPs, channel scaling, modality sum AND the gate blend) runs in ops.se_fuse_blend; a
+SqueezeAndExcitation called on its own (the one-modality networks) runs in ops.se_scale."""
 import torch.nn as nn
 
 from .blocks import normalize_activation
@@ -15,6 +16,11 @@ class SqueezeAndExcitation(nn.Module):
 
     def mlp_params(self):
         return [self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias]
+
+    def forward(self, x):
+        """x * sigmoid(fc(avg_pool(x)))  (model_utils.py:47-51): the module stands alone in the one-modality networks"""
+        from .. import ops
+        return ops.se_scale(x, self.mlp_params(), se_act=self.activation)
 
 
 class SqueezeAndExciteFusionAdd(nn.Module):

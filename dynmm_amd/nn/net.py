@@ -90,12 +90,13 @@ def check_decoder_options(upsampling, encoder_decoder_fusion):
 
 
 def build_decoder_side(model, channels_decoder, nr_decoder_blocks, num_classes, context_module, upsampling,
-                       encoder_decoder_fusion, activation='relu'):
-    """Skip layers, context module and decoder of the three networks (…globalgate.py:145-207, model_skip_mod.py:139-199,
-    model.py:127-187).  encoder_decoder_fusion 'add': skip_layer1..3 = ConvBNAct 1x1 where the channel counts differ,
-    else an empty Sequential; 'None': skip_layer0..3 = nn.Identity and the decoder adds nothing.  The context module
-    resizes with 'nearest' for the learned up-samplings (they only double a map) and with the decoder's mode otherwise."""
-    enc = model.encoder_rgb
+                       encoder_decoder_fusion, activation='relu', encoder=None):
+    """Skip layers, context module and decoder of the networks (…globalgate.py:145-207, model_skip_mod.py:139-199,
+    model.py:127-187, model_one_modality.py:109-163).  encoder_decoder_fusion 'add': skip_layer1..3 = ConvBNAct 1x1 where the
+    channel counts differ, else an empty Sequential; 'None': skip_layer0..3 = nn.Identity and the decoder adds nothing.  The
+    context module resizes with 'nearest' for the learned up-samplings (they only double a map) and with the decoder's mode
+    otherwise.  `encoder`: the trunk whose channel counts size them (default: model.encoder_rgb)."""
+    enc = model.encoder_rgb if encoder is None else encoder
     model.encoder_decoder_fusion = encoder_decoder_fusion
     if encoder_decoder_fusion == 'add':
         for j, (cin, cout) in enumerate(((enc.down_4_channels_out, channels_decoder[2]),

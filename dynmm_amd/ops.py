@@ -2065,6 +2065,142 @@ def se_fuse_blend(rgb, depth, se_params=None, wcum=None, col=0, inplace=False, s
 
 
 # ------------------------------------------------------------------------------------------------
+# single-input squeeze-and-excitation (the one-modality networks; csrc/se_scale.hip)
+# ------------------------------------------------------------------------------------------------
+def _se1_excite(lib, st, x, params, se_act):
+    """squeeze + excitation of x: (s, h, g) — pooled features, saved hidden layer, channel scales [N,C]"""
+    N, Cc, H, W = x.shape
+    f32 = dict(device=x.device, dtype=torch.float32)
+    s, h, g = torch.empty((N, Cc), **f32), torch.empty((N, Cc // 16), **f32), torch.empty((N, Cc), **f32)
+    L.check(lib.dynmm_gap2_fwd(_p(x), None, _p(s), None, N * Cc, H * W, st), 'gap')
+    L.check(lib.dynmm_se1_coeff_fwd(_p(s), _ptr_array(params), _p(h), _p(g), N, Cc, se_act, st), 'se1_coeff_fwd')
+    return s, h, g
+
+
+def _se1_excite_bwd(lib, st, ctx, dg, s, h, g, params):
+    """ds [N,C] and the four parameter gradients (written through _grad_dst) from dg; returns (ds, values for autograd)"""
+    N, Cc = s.shape
+    pairs = [_grad_dst(po) for po in ctx.param_objs]         # straight into the flat .grad views when possible
+    dparams, dparams_ret = [d for d, _ in pairs], [r for _, r in pairs]
+    ds = torch.empty_like(s)
+    ws = torch.empty(lib.dynmm_se1_coeff_bwd_workspace_bytes(N, Cc) // 4, device=s.device, dtype=torch.float32)
+    L.check(lib.dynmm_se1_coeff_bwd(_p(dg), _p(s), _ptr_array(params), _p(h), _p(g), _ptr_array(dparams), _p(ds), _p(ws),
+                                    N, Cc, ctx.se_act, st), 'se1_coeff_bwd')
+    return ds, dparams_ret
+
+
+class _SEScale(Function):
+    """out = x * sigmoid(fc(gap(x)))   (model_utils.py:47-51).  `inplace` (inference only) writes into x's storage."""
+
+    @staticmethod
+    def forward(ctx, x, inplace, se_act, *params):
+        lib = _lib()
+        st = _stream()
+        x = _chk(x, 'x')
+        params = [_chk(p, 'se param') for p in params]
+        N, Cc, H, W = x.shape
+        s, h, g = _se1_excite(lib, st, x, params, se_act)
+        if inplace:
+            out = x
+            ctx.mark_dirty(x)
+        else:
+            out = torch.empty_like(x)
+        L.check(lib.dynmm_se1_scale_fwd(_p(x), _p(g), _p(out), N * Cc, H * W, st), 'se1_scale_fwd')
+        ctx.se_act = se_act
+        ctx.param_objs = list(params)
+        ctx.save_for_backward(x, s, h, g, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib()
+        st = _stream()
+        x, s, h, g = ctx.saved_tensors[:4]
+        params = list(ctx.saved_tensors[4:])
+        gout = _chk(gout, 'grad')
+        N, Cc, H, W = x.shape
+        HW = H * W
+        dg = torch.empty_like(g)
+        L.check(lib.dynmm_se1_scale_bwd_reduce(_p(gout), _p(x), _p(dg), N * Cc, HW, st), 'se1_scale_bwd_reduce')
+        ds, dparams_ret = _se1_excite_bwd(lib, st, ctx, dg, s, h, g, params)
+        dx = torch.empty_like(x)
+        L.check(lib.dynmm_se1_scale_bwd_apply(_p(gout), _p(g), _p(ds), 1.0 / HW, _p(dx), N * Cc, HW, st), 'se1_scale_bwd_apply')
+        _grads_enqueued()
+        return (dx, None, None, *dparams_ret)
+
+
+class _SEScalePool(Function):
+    """max_pool_3x3_s2(x * sigmoid(fc(gap(x)))) — the stem of model_one_modality.py:166-168 without ever writing the
+    full-resolution scaled map, forward or backward (csrc/se_scale.hip: se1_scale_pool_*)."""
+
+    @staticmethod
+    def forward(ctx, x, se_act, *params):
+        lib = _lib()
+        st = _stream()
+        x = _chk(x, 'x')
+        params = [_chk(p, 'se param') for p in params]
+        N, Cc, H, W = x.shape
+        s, h, g = _se1_excite(lib, st, x, params, se_act)
+        y = torch.empty((N, Cc, H // 2, W // 2), device=x.device, dtype=torch.float32)
+        idx = torch.empty((N, Cc, H // 2, W // 2), device=x.device, dtype=torch.int8)
+        L.check(lib.dynmm_se1_scale_pool_fwd(_p(x), _p(g), _p(y), idx.data_ptr(), N * Cc, H, W, st), 'se1_scale_pool_fwd')
+        ctx.se_act = se_act
+        ctx.param_objs = list(params)
+        ctx.save_for_backward(x, s, h, g, idx, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = _lib()
+        st = _stream()
+        x, s, h, g, idx = ctx.saved_tensors[:5]
+        params = list(ctx.saved_tensors[5:])
+        gy = _chk(gy, 'grad')
+        if gy.data_ptr() % 16 != 0:
+            gy = gy.clone()                      # (a gradient view off the 16-byte grid: the kernels read 16 bytes per lane)
+        N, Cc, H, W = x.shape
+        dg = torch.empty_like(g)
+        L.check(lib.dynmm_se1_scale_pool_bwd_reduce(_p(gy), idx.data_ptr(), _p(x), _p(dg), N * Cc, H, W, st),
+                'se1_scale_pool_bwd_reduce')
+        ds, dparams_ret = _se1_excite_bwd(lib, st, ctx, dg, s, h, g, params)
+        dx = torch.empty_like(x)
+        L.check(lib.dynmm_se1_scale_pool_bwd_apply(_p(gy), idx.data_ptr(), _p(g), _p(ds), 1.0 / (H * W), _p(dx), N * Cc, H, W, st),
+                'se1_scale_pool_bwd_apply')
+        _grads_enqueued()
+        return (dx, None, *dparams_ret)
+
+
+def _se1_params(x, se_params):
+    params = tuple(se_params)
+    if len(params) != 4:
+        raise L.DynmmHipError(f'se_scale: se_params must be the 4 tensors (W1, b1, W2, b2), got {len(params)}')
+    if x.dim() != 4 or x.shape[1] % 16 != 0:
+        raise L.DynmmHipError(f'se_scale: x must be [N, C, H, W] with C a multiple of 16, got {tuple(x.shape)}')
+    return params
+
+
+def se_scale(x, se_params, se_act='relu', inplace=False):
+    """x * sigmoid(W2 act(W1 gap(x) + b1) + b2): se_params = (W1, b1, W2, b2) of a SqueezeAndExcitation, se_act its hidden
+    activation.  `inplace` is honoured without autograd only (the backward needs x)."""
+    return _SEScale.apply(x, bool(inplace) and not torch.is_grad_enabled(), ACT[se_act], *_se1_params(x, se_params))
+
+
+def se_scale_pool_supported(x):
+    """even H, W % 8 == 0 (the fused kernels' 16-byte row accesses); se_scale_pool composes the two operators otherwise"""
+    return _FUSED_STEM_POOL and x.dim() == 4 and x.data_ptr() % 16 == 0 and \
+        bool(_lib().dynmm_se1_scale_pool_supported(int(x.shape[2]), int(x.shape[3])))
+
+
+def se_scale_pool(x, se_params, se_act='relu'):
+    """max_pool_3x3_s2(se_scale(x, se_params, se_act)): one pass where the fused kernels serve the shape (values and arg-max
+    decisions are those of the composition), the two operators otherwise."""
+    params = _se1_params(x, se_params)
+    if se_scale_pool_supported(x):
+        return _SEScalePool.apply(x, ACT[se_act], *params)
+    return max_pool_3x3_s2(se_scale(x, params, se_act))
+
+
+# ------------------------------------------------------------------------------------------------
 # SkipESANet: per-stage Gumbel gate + 2-way blend (SURVEY.md §8f-3)
 # ------------------------------------------------------------------------------------------------
 _PHILOX_OFFSET = [0]          # advanced once per gate evaluation that draws its own noise

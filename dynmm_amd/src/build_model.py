@@ -2,13 +2,14 @@
 (FusionDynMM/src/build_model.py:18-218): `--dynamic --global-gate` (SkipGateESANet), `--dynamic` (SkipESANet, per-stage
 Gumbel gates) and the static RGB-D ESANet (no --dynamic, --modality rgbd).  ImageNet / SceneNet weights are read from local
 files (src/pretrained.py; a missing file is an error, never a silent random init).  The single-modality networks
-(`--modality rgb|depth`, ESANetOneModality) are outside the hot path and raise NotImplementedError."""
+(`--modality rgb|depth`, build_model.py:119-141) come from `build_one_modality(args, n_classes)`, to which the drivers dispatch;
+`build_model` itself keeps refusing them."""
 import warnings
 
 import torch
 from torch import nn
 
-from ..nn.esanet import ESANet
+from ..nn.esanet import ESANet, ESANetOneModality
 from ..nn.net import SkipGateESANet
 from ..nn.net_skip import SkipESANet
 from .pretrained import load_scenenet
@@ -48,9 +49,40 @@ def build_model(args, n_classes):
     elif getattr(args, 'modality', 'rgbd') == 'rgbd':
         model = ESANet(**common)                                          # build_model.py:93-113
     else:
-        raise NotImplementedError(f'--modality {args.modality}: the single-modality ESANetOneModality '
-                                  '(src/build_model.py:115-141) is not part of the HIP hot path')
+        raise NotImplementedError(f'--modality {args.modality}: build_model returns the RGB-D networks; the single-modality '
+                                  'ESANetOneModality (src/build_model.py:119-141) is built by build_one_modality(args, n_classes)')
+    return _place_and_initialise(model, args, n_classes, pretrained)
 
+
+def build_one_modality(args, n_classes):
+    """(model, device) for `--modality rgb | depth` (build_model.py:119-141): ESANetOneModality on 3 or 1 input channels, with
+    `--fuse_depth_in_rgb_encoder` as its `weighting_in_encoder`; the same tail as build_model."""
+    if getattr(args, 'modality', 'rgbd') not in ('rgb', 'depth'):
+        raise ValueError(f'build_one_modality: --modality must be rgb or depth, got {getattr(args, "modality", "rgbd")}')
+    if args.dynamic:
+        raise NotImplementedError('--dynamic selects the RGB-D DynMM networks (build_model); it has no single-modality form')
+    pretrained = bool(args.pretrained_on_imagenet) and not args.last_ckpt and args.pretrained_scenenet == ''
+    channels_decoder, nr_decoder_blocks = _decoder_shape(args)
+    model = ESANetOneModality(height=args.height, width=args.width, pretrained_on_imagenet=pretrained, encoder=args.encoder,
+                              encoder_block=args.encoder_block, activation=args.activation,
+                              input_channels=3 if args.modality == 'rgb' else 1,
+                              encoder_decoder_fusion=args.encoder_decoder_fusion, context_module=args.context_module,
+                              num_classes=n_classes, pretrained_dir=args.pretrained_dir, nr_decoder_blocks=nr_decoder_blocks,
+                              channels_decoder=channels_decoder, weighting_in_encoder=args.fuse_depth_in_rgb_encoder,
+                              upsampling=args.upsampling)
+    return _place_and_initialise(model, args, n_classes, pretrained)
+
+
+def build_for_args(args, n_classes):
+    """What the drivers call: build_one_modality for `--modality rgb | depth` without --dynamic (the reference's dispatch,
+    build_model.py:18-141), build_model otherwise."""
+    if not args.dynamic and getattr(args, 'modality', 'rgbd') != 'rgbd':
+        return build_one_modality(args, n_classes)
+    return build_model(args, n_classes)
+
+
+def _place_and_initialise(model, args, n_classes, pretrained):
+    """build_model.py:143-218: device, He init, SceneNet weights, --finetune"""
     device = torch.device('cuda:0') if torch.cuda.is_available() else torch.device('cpu')
     print('Device:', device)
     model.to(device)

@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import dp, engine, schedules
 from .data import SyntheticRGBD, prepare_data
 from .src.args import ArgumentParserRGBDSegmentation
-from .src.build_model import build_model
+from .src.build_model import build_for_args
 from .src.pretrained import load_ckpt
 
 
@@ -62,7 +62,7 @@ def train_main(argv=None):
         os.makedirs(ckpt_dir, exist_ok=True)
         with open(os.path.join(ckpt_dir, 'args.json'), 'w') as f:
             json.dump(vars(args), f, sort_keys=True, indent=4)
-    model, device = build_model(args, n_classes=40)
+    model, device = build_for_args(args, n_classes=40)
     if args.dataset == 'nyuv2':
         train, valid = prepare_data(args, device, rank, world, seed=args.data_seed)
         return run(args, model, train, valid, ckpt_dir, rank, world)

@@ -443,6 +443,35 @@ int dynmm_axpby_pool_bwd_apply(const float* g_out, const signed char* idx_out, c
                                const signed char* idx_depth, const float* a, const float* b, const float* ca,
                                const float* cb, float cscale, float* dxr, float* dxd, int NC, int H, int W, void* stream);
 
+/* ---- single-input squeeze-and-excitation (model_utils.py:36-51; model_one_modality.py:165-187) ----
+ * out = x * g,  g = sigmoid(W2 act(W1 s + b1) + b2),  s = mean_hw x  (the squeeze: dynmm_gap2_fwd(x, NULL, s, NULL, ..)).
+ * Excitation: params / dparams = 4 pointers {W1, b1, W2, b2}, hidden width C/16; h [N,C/16] holds the hidden
+ * pre-activation for the smooth codes and the post-activation for ReLU (dynmm_se_coeff_fwd_act's convention), g [N,C].
+ * Backward: ds [N,C] and the parameter gradients, summed over the samples in a fixed order (no float atomics);
+ * workspace >= dynmm_se1_coeff_bwd_workspace_bytes(N, C). */
+int dynmm_se1_coeff_fwd(const float* s, const float* const* params, float* h, float* g, int N, int C, int act,
+                        void* stream);
+size_t dynmm_se1_coeff_bwd_workspace_bytes(int N, int C);
+int dynmm_se1_coeff_bwd(const float* dg, const float* s, const float* const* params, const float* h, const float* g,
+                        float* const* dparams, float* ds, float* workspace, int N, int C, int act, void* stream);
+/* Scale: out = g[n,c] * x (out may be x: in place);  dg[n,c] = sum_hw gout * x;  dx = g * gout + ds[n,c] * cscale
+ * (ds may be NULL; cscale = 1/HW for the squeeze's backward). */
+int dynmm_se1_scale_fwd(const float* x, const float* g, float* out, int NC, int HW, void* stream);
+int dynmm_se1_scale_bwd_reduce(const float* gout, const float* x, float* dg, int NC, int HW, void* stream);
+int dynmm_se1_scale_bwd_apply(const float* gout, const float* g, const float* ds, float cscale, float* dx, int NC, int HW,
+                              void* stream);
+/* The stem: y = max_pool_3x3_s2(g * x) with the product formed on load — values and arg-max codes are bit-identical to
+ * dynmm_se1_scale_fwd followed by dynmm_maxpool3x3s2_fwd; backward dg = sum_p gy[p] * x[argmax(p)] and
+ * dx = g * max_pool_backward(gy, idx) + ds * cscale in gather form (deterministic, no atomics).  Even H, W % 8 == 0,
+ * 16-byte aligned maps (dynmm_se1_scale_pool_supported); DYNMM_EUNSUPPORTED otherwise: compose scale and pool. */
+int dynmm_se1_scale_pool_supported(int H, int W);
+int dynmm_se1_scale_pool_fwd(const float* x, const float* g, float* y, signed char* idx, int NC, int H, int W,
+                             void* stream);
+int dynmm_se1_scale_pool_bwd_reduce(const float* gy, const signed char* idx, const float* x, float* dg, int NC, int H,
+                                    int W, void* stream);
+int dynmm_se1_scale_pool_bwd_apply(const float* gy, const signed char* idx, const float* g, const float* ds, float cscale,
+                                   float* dx, int NC, int H, int W, void* stream);
+
 /* ---- SkipESANet per-stage gate + 2-way blend (rgb_depth_fusion.py:29-65, model_utils.py:54-70,
  *      model_skip_mod.py:235-311) ----
  * Gate (evaluated when wnext != NULL) from the pooled maps sr,sd [N,C] of the stage's rgb/depth features:
