@@ -556,13 +556,6 @@ extern "C" int dynmm_se_coeff_fwd_act(const float* sr, const float* sd, const fl
     return DYNMM_OK;
 }
 
-extern "C" int dynmm_se_coeff_fwd(const float* sr, const float* sd, const float* const* params,
-                                  const float* wc, int wc_stride, float* a, float* b, float* hr,
-                                  float* hd, float* gr, float* gd, int N, int C, int use_se,
-                                  void* stream) {
-    return dynmm_se_coeff_fwd_act(sr, sd, params, wc, wc_stride, a, b, hr, hd, gr, gd, N, C, use_se, DYNMM_ACT_RELU, stream);
-}
-
 extern "C" size_t dynmm_se_coeff_bwd_workspace_bytes(int N, int C) {
     return sizeof(float) * 2 * (size_t)N * (size_t)(C + C / 16);
 }
@@ -598,15 +591,6 @@ extern "C" int dynmm_se_coeff_bwd_act(const float* da, const float* db, const fl
         return launch_mlp_param_grad(jobs, 2, N, C, Hd, act, st);
     }
     return DYNMM_OK;
-}
-
-extern "C" int dynmm_se_coeff_bwd(const float* da, const float* db, const float* sr, const float* sd,
-                                  const float* const* params, const float* wc, int wc_stride,
-                                  const float* hr, const float* hd, const float* gr, const float* gd,
-                                  float* const* dparams, float* dsr, float* dsd, float* dwc,
-                                  int dwc_stride, float* workspace, int N, int C, int use_se, void* stream) {
-    return dynmm_se_coeff_bwd_act(da, db, sr, sd, params, wc, wc_stride, hr, hd, gr, gd, dparams, dsr, dsd, dwc, dwc_stride,
-                                  workspace, N, C, use_se, DYNMM_ACT_RELU, stream);
 }
 
 static int se1_check(int N, int C, int act) {
@@ -719,16 +703,6 @@ extern "C" int dynmm_reweigh_fwd_act(const float* sr, const float* sd, const flo
     return DYNMM_OK;
 }
 
-extern "C" int dynmm_reweigh_fwd(const float* sr, const float* sd, const float* const* params,
-                                 const float* wblend, int blend_mode, const float* prev,
-                                 int prev_stride, const float* noise, unsigned long long seed,
-                                 unsigned long long offset, float temp, int hard, float* a, float* b,
-                                 float* wnext, float* h, float* g, float* aux, int N, int C,
-                                 void* stream) {
-    return dynmm_reweigh_fwd_act(sr, sd, params, wblend, blend_mode, prev, prev_stride, noise, seed, offset, temp, hard, a, b,
-                                 wnext, h, g, aux, N, C, DYNMM_ACT_RELU, stream);
-}
-
 extern "C" size_t dynmm_reweigh_bwd_workspace_bytes(int N, int C) {
     return sizeof(float) * (size_t)N * (size_t)(2 * C + (2 * C) / 16);
 }
@@ -765,14 +739,4 @@ extern "C" int dynmm_reweigh_bwd_act(const float* d_wnext, const float* da, cons
         return launch_mlp_param_grad(jobs, 1, N, C2, Hd, act, st);
     }
     return DYNMM_OK;
-}
-
-extern "C" int dynmm_reweigh_bwd(const float* d_wnext, const float* da, const float* db,
-                                 const float* sr, const float* sd, const float* const* params,
-                                 const float* prev, int prev_stride, const float* h, const float* g,
-                                 const float* aux, float* const* dparams, float* dsr, float* dsd,
-                                 float* d_wblend, float* d_prev, float* workspace, float temp, int N, int C,
-                                 void* stream) {
-    return dynmm_reweigh_bwd_act(d_wnext, da, db, sr, sd, params, prev, prev_stride, h, g, aux, dparams, dsr, dsd, d_wblend,
-                                 d_prev, workspace, temp, N, C, DYNMM_ACT_RELU, stream);
 }

@@ -118,11 +118,9 @@ SIGNATURES = {
     'dynmm_bilinear_into_fwd': (c_i, [c_f, c_f] + [c_i] * 8 + [c_f]),
     'dynmm_bilinear_into_bwd': (c_i, [c_f, c_f] + [c_i] * 8 + [c_f]),
     'dynmm_gap2_fwd': (c_i, [c_f] * 4 + [c_i, c_i, c_f]),
-    'dynmm_se_coeff_fwd': (c_i, [c_f, c_f, _PP, c_f, c_i] + [c_f] * 6 + [c_i, c_i, c_i, c_f]),
     'dynmm_se_coeff_fwd_act': (c_i, [c_f, c_f, _PP, c_f, c_i] + [c_f] * 6 + [c_i, c_i, c_i, c_i, c_f]),
     'dynmm_se_coeff_bwd_act': (c_i, [c_f] * 4 + [_PP, c_f, c_i] + [c_f] * 4 + [_PP, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     'dynmm_se_coeff_bwd_workspace_bytes': (c_sz, [c_i, c_i]),
-    'dynmm_se_coeff_bwd': (c_i, [c_f] * 4 + [_PP, c_f, c_i] + [c_f] * 4 + [_PP, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_f]),
     'dynmm_axpby_fwd': (c_i, [c_f] * 5 + [c_i, c_i, c_f]),
     'dynmm_axpby_bwd_reduce': (c_i, [c_f] * 5 + [c_i, c_i, c_f]),
     'dynmm_axpby_bwd_apply': (c_i, [c_f] * 5 + [c_fl, c_f, c_f, c_i, c_i, c_f]),
@@ -144,14 +142,11 @@ SIGNATURES = {
     'dynmm_se1_scale_pool_fwd': (c_i, [c_f] * 4 + [c_i] * 3 + [c_f]),
     'dynmm_se1_scale_pool_bwd_reduce': (c_i, [c_f] * 4 + [c_i] * 3 + [c_f]),
     'dynmm_se1_scale_pool_bwd_apply': (c_i, [c_f] * 4 + [c_fl, c_f] + [c_i] * 3 + [c_f]),
-    'dynmm_reweigh_fwd': (c_i, [c_f, c_f, _PP, c_f, c_i, c_f, c_i, c_f, C.c_ulonglong, C.c_ulonglong, c_fl, c_i]
-                          + [c_f] * 6 + [c_i, c_i, c_f]),
     'dynmm_reweigh_fwd_act': (c_i, [c_f, c_f, _PP, c_f, c_i, c_f, c_i, c_f, C.c_ulonglong, C.c_ulonglong, c_fl, c_i]
                               + [c_f] * 6 + [c_i, c_i, c_i, c_f]),
     'dynmm_reweigh_bwd_act': (c_i, [c_f] * 5 + [_PP, c_f, c_i, c_f, c_f, c_f, _PP, c_f, c_f, c_f, c_f, c_f, c_fl, c_i, c_i, c_i,
                                     c_f]),
     'dynmm_reweigh_bwd_workspace_bytes': (c_sz, [c_i, c_i]),
-    'dynmm_reweigh_bwd': (c_i, [c_f] * 5 + [_PP, c_f, c_i, c_f, c_f, c_f, _PP, c_f, c_f, c_f, c_f, c_f, c_fl, c_i, c_i, c_f]),
     'dynmm_gate_head_fwd': (c_i, [c_f] * 8 + [c_i, c_i, c_fl, c_i, c_i, c_f]),
     'dynmm_gate_decide': (c_i, [c_f] * 5 + [c_i, c_f]),
     'dynmm_gate_head_bwd': (c_i, [c_f] * 9 + [c_i, c_i, c_fl, c_f]),
@@ -226,7 +221,7 @@ SIGNATURES = {
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 _lib = None
 
 

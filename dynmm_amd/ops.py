@@ -532,6 +532,12 @@ def _grad_dst(param, like=None):
     return t, t
 
 
+def _grad_dsts(params):
+    """_grad_dst over `params` in their order: (tensors to write into, values to return to autograd)."""
+    pairs = [_grad_dst(po) for po in params]         # straight into the flat .grad views when possible
+    return [d for d, _ in pairs], [r for _, r in pairs]
+
+
 def _grads_enqueued(*streams):
     """The kernels writing the gradients handed out by _grad_dst since the last call are enqueued on `streams`
     (default: the current stream)."""
@@ -1481,11 +1487,16 @@ def adaptive_avg_pool(x, out_hw):
     return _AdaptiveAvgPool.apply(x, oh, ow)
 
 
-class _NearestConcat(Function):
-    """cat([x, nearest(y_1, size(x)), nearest(y_2, size(x)), ...], dim=1)."""
+_INTO = {'nearest': ('dynmm_nearest_into_fwd', 'dynmm_nearest_into_bwd'),
+         'bilinear': ('dynmm_bilinear_into_fwd', 'dynmm_bilinear_into_bwd')}      # bilinear: align_corners=False
+
+
+class _ResizeConcat(Function):
+    """cat([x, resize(y_1, size(x)), resize(y_2, size(x)), ...], dim=1), resize = _INTO[mode]; x itself is the
+    identity copy of dynmm_nearest_into_fwd in every mode."""
 
     @staticmethod
-    def forward(ctx, x, *ys):
+    def forward(ctx, mode, x, *ys):
         lib = _lib()
         st = _stream()
         x = _chk(x, 'x')
@@ -1495,12 +1506,13 @@ class _NearestConcat(Function):
         out = torch.empty((N, Ctot, H, W), device=x.device, dtype=torch.float32)
         off = 0
         ctx.parts = []
-        for t in [x] + ys:
+        for i, t in enumerate([x] + ys):
             _, Cc, h, w = t.shape
-            L.check(lib.dynmm_nearest_into_fwd(_p(t), _p(out), N, Cc, h, w, Ctot, off, H, W, st), 'nearest_into_fwd')
+            name = _INTO['nearest' if i == 0 else mode][0]
+            L.check(getattr(lib, name)(_p(t), _p(out), N, Cc, h, w, Ctot, off, H, W, st), name[6:])
             ctx.parts.append((Cc, h, w, off))
             off += Cc
-        ctx.dims = (N, Ctot, H, W)
+        ctx.dims, ctx.mode = (N, Ctot, H, W), mode
         return out
 
     @staticmethod
@@ -1509,19 +1521,20 @@ class _NearestConcat(Function):
         st = _stream()
         g = _chk(g, 'grad')
         N, Ctot, H, W = ctx.dims
-        outs = []
+        outs = [None]
         for i, (Cc, h, w, off) in enumerate(ctx.parts):
-            if not ctx.needs_input_grad[i]:
+            if not ctx.needs_input_grad[1 + i]:
                 outs.append(None)
                 continue
             d = torch.empty((N, Cc, h, w), device=g.device, dtype=torch.float32)
-            L.check(lib.dynmm_nearest_into_bwd(_p(g), _p(d), N, Cc, h, w, Ctot, off, H, W, st), 'nearest_into_bwd')
+            name = _INTO['nearest' if i == 0 else ctx.mode][1]
+            L.check(getattr(lib, name)(_p(g), _p(d), N, Cc, h, w, Ctot, off, H, W, st), name[6:])
             outs.append(d)
         return tuple(outs)
 
 
 def nearest_concat(x, *ys):
-    return _NearestConcat.apply(x, *ys)
+    return _ResizeConcat.apply('nearest', x, *ys)
 
 
 class _Upsample2xDw(Function):
@@ -1557,14 +1570,11 @@ class _Upsample2xDw(Function):
         if dw is not None:
             nb = lib.dynmm_upsample2x_dw3x3_bwd_workspace_bytes(N, Cc)
             ws = torch.empty(max(nb // 4, 1), device=g.device, dtype=torch.float32)
+        bwd, what = (lib.dynmm_upsample2x_dw3x3_bwd, 'upsample_bwd')
         if ctx.replicate:
             g = _aligned16(g)
-            L.check(lib.dynmm_upsample2x_dw3x3_rep_bwd(_p(g), _p(x), _p(weight), _p(dx), _p(dw), _p(db), _p(ws), N, Cc,
-                                                       H, W, _stream()), 'upsample_rep_bwd')
-            _grads_enqueued()
-            return dx, dw_ret, db_ret, (g if ctx.has_skip else None), None
-        L.check(lib.dynmm_upsample2x_dw3x3_bwd(_p(g), _p(x), _p(weight), _p(dx), _p(dw), _p(db), _p(ws), N, Cc, H, W,
-                                               _stream()), 'upsample_bwd')
+            bwd, what = (lib.dynmm_upsample2x_dw3x3_rep_bwd, 'upsample_rep_bwd')
+        L.check(bwd(_p(g), _p(x), _p(weight), _p(dx), _p(dw), _p(db), _p(ws), N, Cc, H, W, _stream()), what)
         _grads_enqueued()
         return dx, dw_ret, db_ret, (g if ctx.has_skip else None), None
 
@@ -1629,57 +1639,12 @@ def upsample2x(x, mode, skip=None):
     return _Upsample2x.apply(x, skip, mode)
 
 
-class _BilinearConcat(Function):
-    """cat([x, bilinear(y_1, size(x)), bilinear(y_2, size(x)), ...], dim=1), align_corners=False."""
-
-    @staticmethod
-    def forward(ctx, x, *ys):
-        lib = _lib()
-        st = _stream()
-        x = _chk(x, 'x')
-        ys = [_chk(y, 'y') for y in ys]
-        N, C0, H, W = x.shape
-        Ctot = C0 + sum(y.shape[1] for y in ys)
-        out = torch.empty((N, Ctot, H, W), device=x.device, dtype=torch.float32)
-        # x itself: the identity copy of dynmm_nearest_into_fwd
-        L.check(lib.dynmm_nearest_into_fwd(_p(x), _p(out), N, C0, H, W, Ctot, 0, H, W, st), 'nearest_into_fwd')
-        ctx.parts = [(C0, H, W, 0)]
-        off = C0
-        for t in ys:
-            _, Cc, h, w = t.shape
-            L.check(lib.dynmm_bilinear_into_fwd(_p(t), _p(out), N, Cc, h, w, Ctot, off, H, W, st), 'bilinear_into_fwd')
-            ctx.parts.append((Cc, h, w, off))
-            off += Cc
-        ctx.dims = (N, Ctot, H, W)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib()
-        st = _stream()
-        g = _chk(g, 'grad')
-        N, Ctot, H, W = ctx.dims
-        outs = []
-        for i, (Cc, h, w, off) in enumerate(ctx.parts):
-            if not ctx.needs_input_grad[i]:
-                outs.append(None)
-                continue
-            d = torch.empty((N, Cc, h, w), device=g.device, dtype=torch.float32)
-            fn, name = (lib.dynmm_nearest_into_bwd, 'nearest_into_bwd') if i == 0 else \
-                (lib.dynmm_bilinear_into_bwd, 'bilinear_into_bwd')
-            L.check(fn(_p(g), _p(d), N, Cc, h, w, Ctot, off, H, W, st), name)
-            outs.append(d)
-        return tuple(outs)
-
-
 def resize_concat(x, *ys, mode):
     """cat([x, interpolate(y_1, size(x), mode), ...], dim=1): the pyramid pooling concat (context_modules.py:70-87,
     :117-131) for mode 'nearest' (nearest_concat) or 'bilinear' (align_corners=False)."""
-    if mode == 'nearest':
-        return nearest_concat(x, *ys)
-    if mode != 'bilinear':
+    if mode not in _INTO:
         raise NotImplementedError(f'resize_concat: mode must be "nearest" or "bilinear", got {mode!r}')
-    return _BilinearConcat.apply(x, *ys)
+    return _ResizeConcat.apply(mode, x, *ys)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1688,6 +1653,56 @@ def resize_concat(x, *ys, mode):
 def _ptr_array(tensors):
     arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
     return arr
+
+
+def _se2_excite(lib, st, squeeze, params, use_se, se_act, n, Cc, dev, wc_ptr=None, wc_stride=0):
+    """Both excitations and the blend coefficients of a two-input SE fusion over n samples: (checked params, a, b [n,C],
+    saved = (sr, sd, hr, hd, gr, gd)).  squeeze(sr, sd) launches the caller's pooling of its two maps into sr, sd [n,C].
+    use_se False ('add' mode): a, b from wc alone, nothing saved."""
+    f32 = dict(device=dev, dtype=torch.float32)
+    sr = sd = hr = hd = gr = gd = parr = None
+    if use_se:
+        params = [_chk(p, 'se param') for p in params]
+        parr = _ptr_array(params)
+        sr, sd = torch.empty((n, Cc), **f32), torch.empty((n, Cc), **f32)
+        squeeze(sr, sd)
+        hr, hd = torch.empty((n, Cc // 16), **f32), torch.empty((n, Cc // 16), **f32)
+        gr, gd = torch.empty((n, Cc), **f32), torch.empty((n, Cc), **f32)
+    a, b = torch.empty((n, Cc), **f32), torch.empty((n, Cc), **f32)
+    L.check(lib.dynmm_se_coeff_fwd_act(_p(sr), _p(sd), parr, wc_ptr, wc_stride, _p(a), _p(b), _p(hr), _p(hd), _p(gr), _p(gd),
+                                       n, Cc, int(use_se), se_act, st), 'se_coeff_fwd')
+    return list(params), a, b, (sr, sd, hr, hd, gr, gd)
+
+
+def _se2_excite_bwd(lib, st, ctx, da, db, saved, params, wc_ptr=None, wc_stride=0, dwc_ptr=None):
+    """(dsr, dsd [n,C] | None, values for autograd of the 8 parameter gradients) from da, db [n,C]; the parameter
+    gradients are written through _grad_dst in the order of ctx.param_objs, and dwc through dwc_ptr when given."""
+    sr, sd, hr, hd, gr, gd = saved
+    n, Cc = da.shape
+    f32 = dict(device=da.device, dtype=torch.float32)
+    dparams_ret = [None] * len(ctx.param_objs)
+    dsr = dsd = parr = dparr = ws = None
+    if ctx.use_se:
+        dparams, dparams_ret = _grad_dsts(ctx.param_objs)
+        parr, dparr = _ptr_array(params), _ptr_array(dparams)
+        dsr, dsd = torch.empty((n, Cc), **f32), torch.empty((n, Cc), **f32)
+        ws = torch.empty(lib.dynmm_se_coeff_bwd_workspace_bytes(n, Cc) // 4, **f32)
+    L.check(lib.dynmm_se_coeff_bwd_act(_p(da), _p(db), _p(sr), _p(sd), parr, wc_ptr, wc_stride, _p(hr), _p(hd), _p(gr), _p(gd),
+                                       dparr, _p(dsr), _p(dsd), dwc_ptr, wc_stride, _p(ws), n, Cc, int(ctx.use_se), ctx.se_act,
+                                       st), 'se_coeff_bwd')
+    return dsr, dsd, dparams_ret
+
+
+def _fuse_pool_fwd(lib, st, xr, xd, a, b, tr):
+    """(y_out, y_depth, idx_out, idx_depth) of dynmm_axpby_pool_fwd; tr: None, or the stems' BatchNorm scale / shift"""
+    N, Cc, H, W = xr.shape
+    yo = torch.empty((N, Cc, H // 2, W // 2), device=xr.device, dtype=torch.float32)
+    yd = torch.empty_like(yo)
+    io = torch.empty((N, Cc, H // 2, W // 2), device=xr.device, dtype=torch.int8)
+    idd = torch.empty_like(io)
+    L.check(lib.dynmm_axpby_pool_fwd(_p(xr), _p(xd), _p(a), _p(b), _p(yo), io.data_ptr(), _p(yd), idd.data_ptr(),
+                                     _p(tr), Cc, N * Cc, H, W, st), 'axpby_pool_fwd')
+    return yo, yd, io, idd
 
 
 class _SEFuseBlend(Function):
@@ -1708,25 +1723,14 @@ class _SEFuseBlend(Function):
         if n_act > N or tuple(depth.shape[1:]) != tuple(rgb.shape[1:]) or n_act <= 0:
             raise L.DynmmHipError(f'rgb/depth fusion: shape mismatch {tuple(rgb.shape)} vs {tuple(depth.shape)}')
         HW = H * W
-        dev = rgb.device
-        f32 = dict(device=dev, dtype=torch.float32)
         wc_ptr, wc_stride = None, 0
         if wcum is not None:
             wcum = _chk(wcum, 'wcum')
             wc_stride = wcum.shape[1]
             wc_ptr = wcum.data_ptr() + 4 * col
-        sr = sd = hr = hd = gr = gd = None
-        parr = None
-        if use_se:
-            params = [_chk(p, 'se param') for p in params]
-            parr = _ptr_array(params)
-            sr, sd = torch.empty((n_act, Cc), **f32), torch.empty((n_act, Cc), **f32)
-            L.check(lib.dynmm_gap2_fwd(_p(rgb), _p(depth), _p(sr), _p(sd), n_act * Cc, HW, st), 'gap2')
-            hr, hd = torch.empty((n_act, Cc // 16), **f32), torch.empty((n_act, Cc // 16), **f32)
-            gr, gd = torch.empty((n_act, Cc), **f32), torch.empty((n_act, Cc), **f32)
-        a, b = torch.empty((n_act, Cc), **f32), torch.empty((n_act, Cc), **f32)
-        L.check(lib.dynmm_se_coeff_fwd_act(_p(sr), _p(sd), parr, wc_ptr, wc_stride, _p(a), _p(b),
-                                           _p(hr), _p(hd), _p(gr), _p(gd), n_act, Cc, int(use_se), se_act, st), 'se_coeff_fwd')
+        params, a, b, saved = _se2_excite(
+            lib, st, lambda sr, sd: L.check(lib.dynmm_gap2_fwd(_p(rgb), _p(depth), _p(sr), _p(sd), n_act * Cc, HW, st), 'gap2'),
+            params, use_se, se_act, n_act, Cc, rgb.device, wc_ptr, wc_stride)
         if inplace and n_act < N:
             out = rgb                                   # prefix overwritten below, tail untouched
             ctx.mark_dirty(rgb)
@@ -1737,17 +1741,16 @@ class _SEFuseBlend(Function):
         ctx.use_se = use_se
         ctx.se_act = se_act
         ctx.col = col
-        ctx.n_params = len(params)
-        ctx.param_objs = list(params)
-        ctx.save_for_backward(rgb, depth, wcum, a, b, sr, sd, hr, hd, gr, gd, *params)
+        ctx.param_objs = params
+        ctx.save_for_backward(rgb, depth, wcum, a, b, *saved, *params)
         return out
 
     @staticmethod
     def backward(ctx, g):
         lib = _lib()
         st = _stream()
-        rgb, depth, wcum, a, b, sr, sd, hr, hd, gr, gd = ctx.saved_tensors[:11]
-        params = list(ctx.saved_tensors[11:])
+        rgb, depth, wcum, a, b = ctx.saved_tensors[:5]
+        saved, params = ctx.saved_tensors[5:11], list(ctx.saved_tensors[11:])
         g = _chk(g, 'grad')
         N, Cc, H, W = rgb.shape
         n_act = depth.shape[0]
@@ -1755,14 +1758,6 @@ class _SEFuseBlend(Function):
         f32 = dict(device=g.device, dtype=torch.float32)
         da, db = torch.empty((n_act, Cc), **f32), torch.empty((n_act, Cc), **f32)
         L.check(lib.dynmm_axpby_bwd_reduce(_p(g), _p(rgb), _p(depth), _p(da), _p(db), n_act * Cc, HW, st), 'axpby_bwd_reduce')
-        dparams = dparams_ret = [None] * ctx.n_params
-        dsr = dsd = None
-        parr = dparr = None
-        if ctx.use_se:
-            pairs = [_grad_dst(po) for po in ctx.param_objs]     # straight into the flat .grad views when possible
-            dparams, dparams_ret = [d for d, _ in pairs], [r for _, r in pairs]
-            parr, dparr = _ptr_array(params), _ptr_array(dparams)
-            dsr, dsd = torch.empty((n_act, Cc), **f32), torch.empty((n_act, Cc), **f32)
         dwcum = None
         wc_ptr, wc_stride, dwc_ptr = None, 0, None
         if wcum is not None:
@@ -1771,10 +1766,7 @@ class _SEFuseBlend(Function):
             if ctx.needs_input_grad[2]:
                 dwcum = torch.zeros_like(wcum)           # samples past n_act: no gate gradient from this stage
                 dwc_ptr = dwcum.data_ptr() + 4 * ctx.col
-        ws = torch.empty(lib.dynmm_se_coeff_bwd_workspace_bytes(n_act, Cc) // 4, **f32) if ctx.use_se else None
-        L.check(lib.dynmm_se_coeff_bwd_act(_p(da), _p(db), _p(sr), _p(sd), parr, wc_ptr, wc_stride,
-                                           _p(hr), _p(hd), _p(gr), _p(gd), dparr, _p(dsr), _p(dsd),
-                                           dwc_ptr, wc_stride, _p(ws), n_act, Cc, int(ctx.use_se), ctx.se_act, st), 'se_coeff_bwd')
+        dsr, dsd, dparams_ret = _se2_excite_bwd(lib, st, ctx, da, db, saved, params, wc_ptr, wc_stride, dwc_ptr)
         drgb, ddepth = torch.empty_like(rgb), torch.empty_like(depth)
         L.check(lib.dynmm_axpby_bwd_apply(_p(g), _p(a), _p(b), _p(dsr), _p(dsd), 1.0 / HW,
                                           _p(drgb), _p(ddepth), n_act * Cc, HW, st), 'axpby_bwd_apply')
@@ -1794,39 +1786,22 @@ class _SEFusePool(Function):
         rgb, depth = _chk(rgb, 'rgb'), _chk(depth, 'depth')
         _same_shape(rgb, depth, 'stem fusion')
         N, Cc, H, W = rgb.shape
-        HW = H * W
-        f32 = dict(device=rgb.device, dtype=torch.float32)
-        sr = sd = hr = hd = gr = gd = None
-        parr = None
-        if use_se:
-            params = [_chk(p, 'se param') for p in params]
-            parr = _ptr_array(params)
-            sr, sd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-            L.check(lib.dynmm_gap2_fwd(_p(rgb), _p(depth), _p(sr), _p(sd), N * Cc, HW, st), 'gap2')
-            hr, hd = torch.empty((N, Cc // 16), **f32), torch.empty((N, Cc // 16), **f32)
-            gr, gd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-        a, b = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-        L.check(lib.dynmm_se_coeff_fwd_act(_p(sr), _p(sd), parr, None, 0, _p(a), _p(b), _p(hr), _p(hd), _p(gr), _p(gd),
-                                           N, Cc, int(use_se), se_act, st), 'se_coeff_fwd')
-        ctx.se_act = se_act
-        Ho, Wo = H // 2, W // 2
-        yo, yd = torch.empty((N, Cc, Ho, Wo), **f32), torch.empty((N, Cc, Ho, Wo), **f32)
-        io = torch.empty((N, Cc, Ho, Wo), device=rgb.device, dtype=torch.int8)
-        idd = torch.empty_like(io)
-        L.check(lib.dynmm_axpby_pool_fwd(_p(rgb), _p(depth), _p(a), _p(b), _p(yo), io.data_ptr(), _p(yd), idd.data_ptr(),
-                                         None, Cc, N * Cc, H, W, st), 'axpby_pool_fwd')
+        params, a, b, saved = _se2_excite(
+            lib, st, lambda sr, sd: L.check(lib.dynmm_gap2_fwd(_p(rgb), _p(depth), _p(sr), _p(sd), N * Cc, H * W, st), 'gap2'),
+            params, use_se, se_act, N, Cc, rgb.device)
+        yo, yd, io, idd = _fuse_pool_fwd(lib, st, rgb, depth, a, b, None)
         ctx.use_se = use_se
-        ctx.n_params = len(params)
-        ctx.param_objs = list(params)
-        ctx.save_for_backward(rgb, depth, a, b, sr, sd, hr, hd, gr, gd, io, idd, *params)
+        ctx.se_act = se_act
+        ctx.param_objs = params
+        ctx.save_for_backward(rgb, depth, a, b, *saved, io, idd, *params)
         return yo, yd
 
     @staticmethod
     def backward(ctx, g_o, g_d):
         lib = _lib()
         st = _stream()
-        rgb, depth, a, b, sr, sd, hr, hd, gr, gd, io, idd = ctx.saved_tensors[:12]
-        params = list(ctx.saved_tensors[12:])
+        rgb, depth, a, b = ctx.saved_tensors[:4]
+        saved, (io, idd), params = ctx.saved_tensors[4:10], ctx.saved_tensors[10:12], list(ctx.saved_tensors[12:])
         N, Cc, H, W = rgb.shape
         HW = H * W
         f32 = dict(device=rgb.device, dtype=torch.float32)
@@ -1835,18 +1810,7 @@ class _SEFusePool(Function):
         da, db = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
         L.check(lib.dynmm_axpby_pool_bwd_reduce(_p(g_o), io.data_ptr(), _p(rgb), _p(depth), _p(da), _p(db), None, Cc,
                                                 N * Cc, H, W, st), 'axpby_pool_bwd_reduce')
-        dparams = dparams_ret = [None] * ctx.n_params
-        dsr = dsd = None
-        parr = dparr = None
-        if ctx.use_se:
-            pairs = [_grad_dst(po) for po in ctx.param_objs]
-            dparams, dparams_ret = [d for d, _ in pairs], [r for _, r in pairs]
-            parr, dparr = _ptr_array(params), _ptr_array(dparams)
-            dsr, dsd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-        ws = torch.empty(lib.dynmm_se_coeff_bwd_workspace_bytes(N, Cc) // 4, **f32) if ctx.use_se else None
-        L.check(lib.dynmm_se_coeff_bwd_act(_p(da), _p(db), _p(sr), _p(sd), parr, None, 0, _p(hr), _p(hd), _p(gr), _p(gd),
-                                           dparr, _p(dsr), _p(dsd), None, 0, _p(ws), N, Cc, int(ctx.use_se), ctx.se_act, st),
-                'se_coeff_bwd')
+        dsr, dsd, dparams_ret = _se2_excite_bwd(lib, st, ctx, da, db, saved, params)
         drgb, ddepth = torch.empty_like(rgb), torch.empty_like(depth)
         L.check(lib.dynmm_axpby_pool_bwd_apply(_p(g_o), io.data_ptr(), _p(g_d), idd.data_ptr(), _p(a), _p(b), _p(dsr), _p(dsd),
                                                1.0 / HW, _p(drgb), _p(ddepth), N * Cc, H, W, st), 'axpby_pool_bwd_apply')
@@ -1888,37 +1852,25 @@ class _StemBNFusePool(Function):
                 L.check(lib.dynmm_bn_stats(_p(x), _p(sums), N, Cc, HW, zeroed, st), 'bn_stats')
             L.check(lib.dynmm_bn_finalize(_p(sums), _p(gam), _p(bet), _p(rm), _p(rv), _p(stats[2 * k]), _p(stats[2 * k + 1]),
                                           _p(nbt), _p(tr[2 * k]), _p(tr[2 * k + 1]), N, Cc, HW, eps, mom, st), 'bn_finalize')
-        sr = sd = hr = hd = gr = gd = None
-        parr = None
-        if use_se:
-            params = [_chk(p, 'se param') for p in params]
-            parr = _ptr_array(params)
-            sr, sd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-            L.check(lib.dynmm_gap2_bnrelu_fwd(_p(xr), _p(xd), _p(tr), Cc, _p(sr), _p(sd), N * Cc, HW, st), 'gap2_bnrelu')
-            hr, hd = torch.empty((N, Cc // 16), **f32), torch.empty((N, Cc // 16), **f32)
-            gr, gd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-        a, b = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-        L.check(lib.dynmm_se_coeff_fwd(_p(sr), _p(sd), parr, None, 0, _p(a), _p(b), _p(hr), _p(hd), _p(gr), _p(gd),
-                                       N, Cc, int(use_se), st), 'se_coeff_fwd')
-        Ho, Wo = H // 2, W // 2
-        yo, yd = torch.empty((N, Cc, Ho, Wo), **f32), torch.empty((N, Cc, Ho, Wo), **f32)
-        io = torch.empty((N, Cc, Ho, Wo), device=dev, dtype=torch.int8)
-        idd = torch.empty_like(io)
-        L.check(lib.dynmm_axpby_pool_fwd(_p(xr), _p(xd), _p(a), _p(b), _p(yo), io.data_ptr(), _p(yd), idd.data_ptr(),
-                                         _p(tr), Cc, N * Cc, H, W, st), 'axpby_pool_fwd')
+        ctx.se_act = ACT['relu']                 # the stems' SE excitations: ReLU only (stem_bn_fuse_supported)
+        params, a, b, saved = _se2_excite(
+            lib, st, lambda sr, sd: L.check(lib.dynmm_gap2_bnrelu_fwd(_p(xr), _p(xd), _p(tr), Cc, _p(sr), _p(sd), N * Cc, HW, st),
+                                            'gap2_bnrelu'),
+            params, use_se, ctx.se_act, N, Cc, dev)
+        yo, yd, io, idd = _fuse_pool_fwd(lib, st, xr, xd, a, b, tr)
         ctx.use_se = use_se
-        ctx.n_params = len(params)
-        ctx.param_objs = list(params)
+        ctx.param_objs = params
         ctx.bn_params = (gam_r, bet_r, gam_d, bet_d)
         ctx.slots = slots
-        ctx.save_for_backward(xr, xd, tr, stats, a, b, sr, sd, hr, hd, gr, gd, io, idd, gam_r, bet_r, gam_d, bet_d, *params)
+        ctx.save_for_backward(xr, xd, tr, stats, a, b, *saved, io, idd, gam_r, bet_r, gam_d, bet_d, *params)
         return yo, yd
 
     @staticmethod
     def backward(ctx, g_o, g_d):
         lib = _lib()
         st = _stream()
-        xr, xd, tr, stats, a, b, sr, sd, hr, hd, gr, gd, io, idd, gam_r, bet_r, gam_d, bet_d = ctx.saved_tensors[:18]
+        xr, xd, tr, stats, a, b = ctx.saved_tensors[:6]
+        saved, (io, idd, gam_r, bet_r, gam_d, bet_d) = ctx.saved_tensors[6:12], ctx.saved_tensors[12:18]
         params = list(ctx.saved_tensors[18:])
         N, Cc, H, W = xr.shape
         HW = H * W
@@ -1929,17 +1881,7 @@ class _StemBNFusePool(Function):
         da, db = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
         L.check(lib.dynmm_axpby_pool_bwd_reduce(_p(g_o), io.data_ptr(), _p(xr), _p(xd), _p(da), _p(db), _p(tr), Cc,
                                                 N * Cc, H, W, st), 'axpby_pool_bwd_reduce')
-        dparams = dparams_ret = [None] * ctx.n_params
-        dsr = dsd = None
-        parr = dparr = None
-        if ctx.use_se:
-            pairs = [_grad_dst(po) for po in ctx.param_objs]
-            dparams, dparams_ret = [d for d, _ in pairs], [r for _, r in pairs]
-            parr, dparr = _ptr_array(params), _ptr_array(dparams)
-            dsr, dsd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
-        ws = torch.empty(lib.dynmm_se_coeff_bwd_workspace_bytes(N, Cc) // 4, **f32) if ctx.use_se else None
-        L.check(lib.dynmm_se_coeff_bwd(_p(da), _p(db), _p(sr), _p(sd), parr, None, 0, _p(hr), _p(hd), _p(gr), _p(gd),
-                                       dparr, _p(dsr), _p(dsd), None, 0, _p(ws), N, Cc, int(ctx.use_se), st), 'se_coeff_bwd')
+        dsr, dsd, dparams_ret = _se2_excite_bwd(lib, st, ctx, da, db, saved, params)
         _grads_enqueued()        # the SE parameters' gradients are complete HERE, on this stream: reported now, not by whichever
                                  # op next calls _grads_enqueued (the deferred branch below returns without one: ADVICE r5)
         # BatchNorm backward of both stems with their incoming gradient derived on the fly from the pooled gradients
@@ -2032,20 +1974,16 @@ def stem_bn_fuse_pool(x_rgb, bn_rgb, x_depth, bn_depth, se_params=None):
                                  *(tuple(se_params) if use_se else ()))
 
 
-_FUSED_STEM_POOL = True        # (module attributes: tests compare the fused stem with the unfused ops)
-_FUSED_STEM_BN = True
-
-
 def stem_bn_fuse_supported(h, w, bn_a, bn_b, act='relu'):
     """h, w: spatial size of the stem conv outputs.  The fused stem tail applies BatchNorm + ReLU on load: ReLU only."""
-    return ACT[act] == L.ACT_RELU and _FUSED_STEM_BN and _FUSED_STEM_POOL and bool(_lib().dynmm_axpby_pool_supported(int(h), int(w))) and \
+    return ACT[act] == L.ACT_RELU and bool(_lib().dynmm_axpby_pool_supported(int(h), int(w))) and \
         bn_a.training and bn_b.training and torch.is_grad_enabled() and bn_a.momentum is not None and \
         bn_b.momentum is not None
 
 
 def se_fuse_pool_supported(x):
     """even H, W % 8 == 0 (the kernels' 16-byte row accesses); otherwise callers compose the unfused ops"""
-    return _FUSED_STEM_POOL and x.dim() == 4 and bool(_lib().dynmm_axpby_pool_supported(int(x.shape[2]), int(x.shape[3])))
+    return x.dim() == 4 and bool(_lib().dynmm_axpby_pool_supported(int(x.shape[2]), int(x.shape[3])))
 
 
 def se_fuse_pool(rgb, depth, se_params=None, se_act='relu'):
@@ -2080,8 +2018,7 @@ def _se1_excite(lib, st, x, params, se_act):
 def _se1_excite_bwd(lib, st, ctx, dg, s, h, g, params):
     """ds [N,C] and the four parameter gradients (written through _grad_dst) from dg; returns (ds, values for autograd)"""
     N, Cc = s.shape
-    pairs = [_grad_dst(po) for po in ctx.param_objs]         # straight into the flat .grad views when possible
-    dparams, dparams_ret = [d for d, _ in pairs], [r for _, r in pairs]
+    dparams, dparams_ret = _grad_dsts(ctx.param_objs)
     ds = torch.empty_like(s)
     ws = torch.empty(lib.dynmm_se1_coeff_bwd_workspace_bytes(N, Cc) // 4, device=s.device, dtype=torch.float32)
     L.check(lib.dynmm_se1_coeff_bwd(_p(dg), _p(s), _ptr_array(params), _p(h), _p(g), _ptr_array(dparams), _p(ds), _p(ws),
@@ -2187,7 +2124,7 @@ def se_scale(x, se_params, se_act='relu', inplace=False):
 
 def se_scale_pool_supported(x):
     """even H, W % 8 == 0 (the fused kernels' 16-byte row accesses); se_scale_pool composes the two operators otherwise"""
-    return _FUSED_STEM_POOL and x.dim() == 4 and x.data_ptr() % 16 == 0 and \
+    return x.dim() == 4 and x.data_ptr() % 16 == 0 and \
         bool(_lib().dynmm_se1_scale_pool_supported(int(x.shape[2]), int(x.shape[3])))
 
 
@@ -2285,8 +2222,7 @@ class _ReweighFuse(Function):
         gate_bwd = gate and d_wnext is not None
         if gate_bwd:
             d_wnext = _chk(d_wnext, 'd_wnext')
-            pairs = [_grad_dst(po) for po in ctx.param_objs]
-            dparams, dparams_ret = [d for d, _ in pairs], [r for _, r in pairs]
+            dparams, dparams_ret = _grad_dsts(ctx.param_objs)
             parr, dparr = _ptr_array(params), _ptr_array(dparams)
             dsr, dsd = torch.empty((N, Cc), **f32), torch.empty((N, Cc), **f32)
             if prev is not None and ctx.needs_input_grad[3]:

@@ -368,27 +368,16 @@ int dynmm_bilinear_into_bwd(const float* g_out, float* dy, int N, int C, int h, 
 /* s[n,c] = mean_hw x[n,c,:]  for two tensors at once. */
 int dynmm_gap2_fwd(const float* xr, const float* xd, float* sr, float* sd, int NC, int HW, void* stream);
 /* Per-sample SE MLPs and blend coefficients:
- *   g_m = sigmoid(W2_m relu(W1_m s_m + b1_m) + b2_m)  (m in {rgb, depth});  use_se=0 -> g = 1
+ *   g_m = sigmoid(W2_m act(W1_m s_m + b1_m) + b2_m)  (m in {rgb, depth});  use_se=0 -> g = 1
  *   a = wc + (1-wc) g_r ;  b = (1-wc) g_d           (wc[n] optional, NULL -> 0)
  * so that  out = a*rgb + b*depth  ==  wc*rgb + (1-wc)*(rgb*g_r + depth*g_d).
- * params: 8 pointers {W1r,b1r,W2r,b2r,W1d,b1d,W2d,b2d}; hidden = C/16.
- * saves h_r,h_d [N,C/16] and g_r,g_d [N,C] for the backward. */
-int dynmm_se_coeff_fwd(const float* sr, const float* sd, const float* const* params,
-                       const float* wc, int wc_stride, float* a, float* b,
-                       float* hr, float* hd, float* gr, float* gd,
-                       int N, int C, int use_se, void* stream);
-/* backward: per-sample pass (pre-activation gradients of both MLPs into `workspace`,
+ * params: 8 pointers {W1r,b1r,W2r,b2r,W1d,b1d,W2d,b2d}; hidden = C/16; act: the hidden activation (DYNMM_ACT_*).
+ * saves h_r,h_d [N,C/16] and g_r,g_d [N,C] for the backward.  For the smooth codes hr / hd hold the hidden PRE-activation
+ * W1 s + b1 (ReLU: the post-activation) — pass the forward's buffers and the forward's `act` to the backward.
+ * backward: per-sample pass (pre-activation gradients of both MLPs into `workspace`,
  * >= dynmm_se_coeff_bwd_workspace_bytes(N, C); pooled gradients dsr/dsd; dwc) followed by the parameter
  * gradients summed over the samples in a fixed order — no float atomics, bit-reproducible. */
 size_t dynmm_se_coeff_bwd_workspace_bytes(int N, int C);
-int dynmm_se_coeff_bwd(const float* da, const float* db, const float* sr, const float* sd,
-                       const float* const* params, const float* wc, int wc_stride,
-                       const float* hr, const float* hd, const float* gr, const float* gd,
-                       float* const* dparams, float* dsr, float* dsd, float* dwc, int dwc_stride,
-                       float* workspace, int N, int C, int use_se, void* stream);
-/* The same pair with the hidden activation as an argument (the two above are act = DYNMM_ACT_RELU).  For the smooth codes
- * hr / hd hold the hidden PRE-activation W1 s + b1 (ReLU: the post-activation, as above) — pass the forward's buffers and
- * the forward's `act` to the backward. */
 int dynmm_se_coeff_fwd_act(const float* sr, const float* sd, const float* const* params,
                            const float* wc, int wc_stride, float* a, float* b,
                            float* hr, float* hd, float* gr, float* gd,
@@ -475,7 +464,7 @@ int dynmm_se1_scale_pool_bwd_apply(const float* gy, const signed char* idx, cons
 /* ---- SkipESANet per-stage gate + 2-way blend (rgb_depth_fusion.py:29-65, model_utils.py:54-70,
  *      model_skip_mod.py:235-311) ----
  * Gate (evaluated when wnext != NULL) from the pooled maps sr,sd [N,C] of the stage's rgb/depth features:
- *   p = [sr; sd];  g = sigmoid(W2 relu(W1 p + b1) + b2);  s = sum_c g[c] p[c] / 2C  (== mean(x*g));
+ *   p = [sr; sd];  g = sigmoid(W2 act(W1 p + b1) + b2);  s = sum_c g[c] p[c] / 2C  (== mean(x*g));
  *   w = sigmoid(s);  y = gumbel_softmax([w, 1-w]/temp, tau=1, hard)  with Gumbel noise G = -log E:
  *   E[n,2] ~ Exp(1) taken from `noise` when given, else drawn by Philox4x32-10 keyed (seed; n, offset);
  *   prev (stride prev_stride, optional): b1 = y1*prev, b0 = 1-b1.   wnext[N,2] = (b0,b1) or y.
@@ -484,20 +473,10 @@ int dynmm_se1_scale_pool_bwd_apply(const float* gy, const signed char* idx, cons
  * Blend coefficients (written when a != NULL) for out = a*rgb + b*depth:
  *   blend_mode 0: rgb only (1,0);  1: rgb+depth (1,1);  2: w0*rgb + w1*(rgb+depth) -> (w0+w1, w1)
  *   with wblend[N,2].  The backward returns d_wblend from da,db of dynmm_axpby_bwd_reduce, the pooled
- *   gradients dsr,dsd (to be fed to dynmm_axpby_bwd_apply), the 4 parameter gradients and d_prev[N]. */
-int dynmm_reweigh_fwd(const float* sr, const float* sd, const float* const* params,
-                      const float* wblend, int blend_mode, const float* prev, int prev_stride,
-                      const float* noise, unsigned long long seed, unsigned long long offset,
-                      float temp, int hard, float* a, float* b, float* wnext, float* h, float* g,
-                      float* aux, int N, int C, void* stream);
+ *   gradients dsr,dsd (to be fed to dynmm_axpby_bwd_apply), the 4 parameter gradients and d_prev[N].
+ * act: the hidden activation of the gate's excitation; h holds the hidden pre-activation for the smooth codes, as
+ * dynmm_se_coeff_fwd_act's. */
 size_t dynmm_reweigh_bwd_workspace_bytes(int N, int C);
-int dynmm_reweigh_bwd(const float* d_wnext, const float* da, const float* db, const float* sr,
-                      const float* sd, const float* const* params, const float* prev, int prev_stride,
-                      const float* h, const float* g, const float* aux, float* const* dparams,
-                      float* dsr, float* dsd, float* d_wblend, float* d_prev, float* workspace, float temp,
-                      int N, int C, void* stream);
-/* The same pair with the hidden activation of the gate's excitation as an argument (above: DYNMM_ACT_RELU); h holds the
- * hidden pre-activation for the smooth codes, as dynmm_se_coeff_fwd_act's. */
 int dynmm_reweigh_fwd_act(const float* sr, const float* sd, const float* const* params,
                           const float* wblend, int blend_mode, const float* prev, int prev_stride,
                           const float* noise, unsigned long long seed, unsigned long long offset,
