@@ -62,6 +62,28 @@ __device__ __forceinline__ T block_reduce_sum_256(T v, T* smem) {
     return r;
 }
 
+// r[0 .. N-1] = p[0 .. N-1] in the widest units N allows (the attention kernels' LDS rows: one address for every lane, a
+// broadcast); p: aligned to the widest unit used
+template <int N>
+__device__ __forceinline__ void row_ld(const float* __restrict__ p, float r[N]) {
+    if constexpr (N % 4 == 0) {
+#pragma unroll
+        for (int q = 0; q < N / 4; ++q) {
+            const float4 t = reinterpret_cast<const float4*>(p)[q];
+            r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w;
+        }
+    } else if constexpr (N % 2 == 0) {
+#pragma unroll
+        for (int q = 0; q < N / 2; ++q) {
+            const float2 t = reinterpret_cast<const float2*>(p)[q];
+            r[2 * q] = t.x; r[2 * q + 1] = t.y;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < N; ++q) r[q] = p[q];
+    }
+}
+
 // Swish z * sigmoid(z) and Hswish z * relu6(z + 3) / 6 (model_utils.py:100-115), in the reference's order of operations.
 // (z -> -inf: expf(-z) = +inf, the quotient is -0: finite, no NaN.)
 __device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + expf(-v)); }

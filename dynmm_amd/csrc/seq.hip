@@ -2,7 +2,9 @@
 // GEMMs.  Every Linear / Conv1d(k=1) of those experts is a 1x1 convolution over tokens and runs on the
 // implicit-GEMM MFMA kernels of conv_igemm.hip with activations laid out [B, D, T] (= NCHW with H = 1, W = T,
 // exactly the layout the reference produces with x.permute([0, 2, 1]) in front of its Conv1d).  This file adds
-//   * LayerNorm over the channel axis D of [B, D, T] (post-norm TransformerEncoderLayer), forward + backward,
+//   * LayerNorm over the channel axis D of [B, D, T], forward + backward: the post-norm TransformerEncoderLayer
+//     (dynmm_layernorm_*) and MULT's pre-norm layers, whose launch returns `res + dropout(x)` AND its normalisation
+//     (dynmm_prenorm_*), on one kernel family,
 //   * multi-head self-attention for short sequences (T <= 64): one wave per (sample, head), Q K V and the
 //     T x T probabilities stay in LDS, forward + backward,
 //   * the mixture head: DiffSoftmax gate over K experts (affect_dyn.py:18-28), blend, L1 loss, gate regulariser
@@ -47,13 +49,16 @@ __device__ __forceinline__ float ln_group_sum(float v, float (*sh)[kLnTok], int 
 
 // `nparts` > 1 / `xbias`: x arrives as partial sums (the hidden-unit split of ffn_kernel) plus a per-channel bias; the sum is
 // formed once, in slab order, written to `xsum` (the backward's `x`) and used from there.
+// Pre-norm callers: `x` may be null (the value is res, which they require), `vsum` (optional) receives the normalised value
+// dropout(x) + res, and without `gamma` the launch ends after that store (the residual sum alone).
 template <int NP>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                      const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, float* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd, int B, int D,
                                                      int T, float eps, const DropSpec spec, int nparts, size_t pstride,
-                                                     const float* __restrict__ xbias, float* __restrict__ xsum) {
+                                                     const float* __restrict__ xbias, float* __restrict__ xsum,
+                                                     float* __restrict__ vsum) {
     __shared__ float sh[kLnGrp][kLnTok];
     const DropState ds(spec);
     const int tl = threadIdx.x & (kLnTok - 1), grp = threadIdx.x / kLnTok;
@@ -61,6 +66,8 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
     const bool ok = tok < B * T;
     const int b = ok ? tok / T : 0, t = ok ? tok - b * T : 0;
     const size_t base = (size_t)b * D * T + t;
+    const float* gp = gamma ? gamma : res;                      // (clamped, in-range reads either way; unused without gamma)
+    const float* bp = gamma ? beta : res;
     float v[NP][kLnCh], gm[NP][kLnCh], bt[NP][kLnCh];
     float s = 0.f;
     // (loads are unconditional on clamped addresses and the values selected afterwards: a predicate per element is a divergent
@@ -74,18 +81,18 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
         for (int e = 0; e < kLnCh; ++e) {
             const int cc = min(c8 * kLnCh + e, D - 1);
             const size_t i = base + (size_t)cc * T;
-            xv[e] = x[i];
+            xv[e] = x ? x[i] : 0.f;
             rv[e] = res ? res[i] : 0.f;
-            gm[pp][e] = gamma[cc];                              // (used after the two reductions: requested here)
-            bt[pp][e] = beta[cc];
+            gm[pp][e] = gp[gamma ? cc : 0];                     // (used after the two reductions: requested here)
+            bt[pp][e] = bp[gamma ? cc : 0];
         }
         if (xsum) {
             // slab-major: the eight loads of a slab are in flight together (channel-major, the slab loop of each channel was a
             // chain of dependent round trips — 30 us per launch at eight slabs)
             float bv[kLnCh];
-            const float* bp = xbias ? xbias : gamma;
+            const float* xb = xbias ? xbias : gamma;
 #pragma unroll
-            for (int e = 0; e < kLnCh; ++e) bv[e] = bp[min(c8 * kLnCh + e, D - 1)];
+            for (int e = 0; e < kLnCh; ++e) bv[e] = xb[min(c8 * kLnCh + e, D - 1)];
             for (int q = 1; q < nparts; ++q) {
                 const float* xq = x + (size_t)q * pstride;
 #pragma unroll
@@ -100,11 +107,14 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
         }
 #pragma unroll
         for (int e = 0; e < kLnCh; ++e) {
-            const bool valid = ok && c8 * kLnCh + e < D;
+            const int c = c8 * kLnCh + e;
+            const bool valid = ok && c < D;
             v[pp][e] = valid ? xv[e] * k[e] + rv[e] : 0.f;
             s += v[pp][e];
+            if (valid && vsum) vsum[base + (size_t)c * T] = v[pp][e];
         }
     }
+    if (!gamma) return;                                         // (uniform over the launch)
     const float mu = ln_group_sum(s, sh, tl, grp) / (float)D;
     float q = 0.f;
 #pragma unroll
@@ -133,13 +143,15 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
 // dx = rstd * (g*gamma - mean_c(g*gamma) - xhat * mean_c(g*gamma*xhat)); the same thread layout and register cache as the
 // forward.  `part` (optional, [gridDim.x][2][D]): this workgroup's 16-token sums of g * xhat and g per channel — the
 // parameter gradients without a second pass over g, x and res (ln_param_reduce_kernel adds the workgroups' rows in order).
-template <int NP>
+// SUMMED (the pre-norm layer, which saved its sum): `x` already is dropout(x) + res, so xhat needs neither the keep factor nor
+// `res`, and `gs` (optional), the gradient that reaches the sum directly, is added to the result.
+template <int NP, bool SUMMED = false>
 __global__ void __launch_bounds__(256) ln_bwd_dx_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                                         const float* __restrict__ res,
                                                         const float* __restrict__ gamma, const float* __restrict__ mean,
                                                         const float* __restrict__ rstd, float* __restrict__ dx,
                                                         float* __restrict__ dres, float* __restrict__ part, int B, int D,
-                                                        int T, const DropSpec spec) {
+                                                        int T, const DropSpec spec, const float* __restrict__ gs) {
     __shared__ float sh[kLnGrp][kLnTok];
     const DropState ds(spec);
     const int tl = threadIdx.x & (kLnTok - 1), grp = threadIdx.x / kLnTok;
@@ -148,7 +160,7 @@ __global__ void __launch_bounds__(256) ln_bwd_dx_kernel(const float* __restrict_
     const int b = ok ? tok / T : 0, t = ok ? tok - b * T : 0;
     const size_t base = (size_t)b * D * T + t;
     const float mu = ok ? mean[tok] : 0.f, rs = ok ? rstd[tok] : 0.f;
-    float gv[NP][kLnCh], xh[NP][kLnCh], kk[NP][kLnCh], gm[NP][kLnCh];
+    float gv[NP][kLnCh], xh[NP][kLnCh], kk[NP][kLnCh], gm[NP][kLnCh], sv[NP][kLnCh];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int pp = 0; pp < NP; ++pp) {
@@ -160,15 +172,17 @@ __global__ void __launch_bounds__(256) ln_bwd_dx_kernel(const float* __restrict_
             const int cc = min(c8 * kLnCh + e, D - 1);
             const size_t i = base + (size_t)cc * T;
             gv[pp][e] = g[i];
+            if constexpr (SUMMED) sv[pp][e] = gs ? gs[i] : 0.f;
             xv[e] = x[i];
-            rv[e] = res ? res[i] : 0.f;
+            if constexpr (!SUMMED) rv[e] = res ? res[i] : 0.f;
             gm[pp][e] = gamma[cc];
         }
 #pragma unroll
         for (int e = 0; e < kLnCh; ++e) {
             const bool valid = ok && c8 * kLnCh + e < D;
             gv[pp][e] = valid ? gv[pp][e] : 0.f;
-            xh[pp][e] = valid ? (xv[e] * kk[pp][e] + rv[e] - mu) * rs : 0.f;
+            if constexpr (SUMMED) xh[pp][e] = valid ? (xv[e] - mu) * rs : 0.f;
+            else xh[pp][e] = valid ? (xv[e] * kk[pp][e] + rv[e] - mu) * rs : 0.f;
             const float gg = gv[pp][e] * gm[pp][e];
             s1 += gg;
             s2 += gg * xh[pp][e];
@@ -184,7 +198,8 @@ __global__ void __launch_bounds__(256) ln_bwd_dx_kernel(const float* __restrict_
             const int c = (pp * kLnGrp + grp) * kLnCh + e;
             if (ok && c < D) {
                 const size_t i = base + (size_t)c * T;
-                const float dv = rs * (gv[pp][e] * gm[pp][e] - s1 - xh[pp][e] * s2);
+                float dv = rs * (gv[pp][e] * gm[pp][e] - s1 - xh[pp][e] * s2);
+                if constexpr (SUMMED) dv += sv[pp][e];
                 if (dres) dres[i] = dv;
                 if (dx) dx[i] = dv * kk[pp][e];
             }
@@ -213,9 +228,12 @@ __global__ void __launch_bounds__(256) ln_bwd_dx_kernel(const float* __restrict_
 
 // dgamma[c], dbeta[c] = sum over the workgroups' rows of ln_bwd_dx_kernel's `part`, in a fixed order (deterministic):
 // workgroup = 4 of the 2 D columns x a 64-way split of the rows (lane = split: at 400 rows a thread adds 7 values), the 64
-// splits of a column meet in a wave butterfly.
+// splits of a column meet in a wave butterfly.  `accumulate`: the sums are ADDED to dgamma / dbeta (a LayerNorm applied to
+// several inputs in one step: the launches of one stream run in order, one thread owns a column, so the result is still a
+// fixed-order sum).
 __global__ void __launch_bounds__(256) ln_param_reduce_kernel(const float* __restrict__ part, int nrows, int D,
-                                                              float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                              int accumulate) {
     const int sp = threadIdx.x & 63;
     const int col = blockIdx.x * 4 + (threadIdx.x >> 6);           // 0 .. 2D-1, one wave per column
     if (col >= 2 * D) return;
@@ -225,8 +243,8 @@ __global__ void __launch_bounds__(256) ln_param_reduce_kernel(const float* __res
     for (int r = sp * per; r < r1; ++r) s += part[(size_t)r * 2 * D + col];
     s = wave_reduce_sum<float>(s);
     if (sp == 0) {
-        if (col < D) dgamma[col] = s;
-        else dbeta[col - D] = s;
+        float* dst = col < D ? dgamma + col : dbeta + (col - D);
+        *dst = accumulate ? *dst + s : s;
     }
 }
 
@@ -273,26 +291,6 @@ __global__ void __launch_bounds__(256) ln_bwd_param_kernel(const float* __restri
 //   * the CHANNELS in the phases that are sums over keys (P'V; dQ, dK, dV): wave w owns channels w * CS .. + CS - 1 of every
 //     query — no partial sums to combine.
 // Row maxima / denominators / dot products meet in a [NW][64] LDS array.
-template <int N>
-__device__ __forceinline__ void mha_ld(const float* __restrict__ p, float r[N]) {      // p: aligned to the widest unit used
-    if constexpr (N % 4 == 0) {
-#pragma unroll
-        for (int q = 0; q < N / 4; ++q) {
-            const float4 t = reinterpret_cast<const float4*>(p)[q];
-            r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w;
-        }
-    } else if constexpr (N % 2 == 0) {
-#pragma unroll
-        for (int q = 0; q < N / 2; ++q) {
-            const float2 t = reinterpret_cast<const float2*>(p)[q];
-            r[2 * q] = t.x; r[2 * q + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < N; ++q) r[q] = p[q];
-    }
-}
-
 // copy between a [T][T] global tile and the [T][ld] LDS tile, NT consecutive elements per step (coalesced)
 template <bool TO_LDS, int NT>
 __device__ __forceinline__ void mha_tile_copy(float* __restrict__ gl, float* lds, int T, int ld, const float* rowscale) {
@@ -356,7 +354,7 @@ __global__ void __launch_bounds__(64 * NW) mha_fwd_kernel(const float* __restric
     if (act)
         for (int j = j_lo; j < j_hi; ++j) {
             float kr[DH];
-            mha_ld<DH>(ks + j * DH, kr);
+            row_ld<DH>(ks + j * DH, kr);
             float sc = 0.f;
 #pragma unroll
             for (int c = 0; c < DH; ++c) sc += q[c] * kr[c];
@@ -397,7 +395,7 @@ __global__ void __launch_bounds__(64 * NW) mha_fwd_kernel(const float* __restric
         for (int e = 0; e < CS; ++e) o[e] = 0.f;
         for (int j = 0; j < T; ++j) {
             float vr[CS];
-            mha_ld<CS>(vs + j * DH + w * CS, vr);
+            row_ld<CS>(vs + j * DH + w * CS, vr);
             const float pj = pkr[j];
 #pragma unroll
             for (int e = 0; e < CS; ++e) o[e] += pj * vr[e];
@@ -465,7 +463,7 @@ __global__ void __launch_bounds__(64 * NW) mha_bwd_kernel(const float* __restric
     unsigned long long kept = 0ull;                              // this wave's keep decisions of row i (bit j), drawn once
     if (act) {
         float gq[DH];                                            // dOut column of query i
-        mha_ld<DH>(gs + i * DH, gq);
+        row_ld<DH>(gs + i * DH, gq);
         for (int j0 = j_lo; j0 < j_hi; j0 += 8) {
             float kp[8];
             drop.row8(row, j0 >> 3, T, kp);
@@ -474,7 +472,7 @@ __global__ void __launch_bounds__(64 * NW) mha_bwd_kernel(const float* __restric
                 const int j = j0 + e;
                 if (j < T) {
                     float vr[DH];
-                    mha_ld<DH>(vs + j * DH, vr);
+                    row_ld<DH>(vs + j * DH, vr);
                     float sacc = 0.f;
 #pragma unroll
                     for (int c = 0; c < DH; ++c) sacc += gq[c] * vr[c];
@@ -506,9 +504,9 @@ __global__ void __launch_bounds__(64 * NW) mha_bwd_kernel(const float* __restric
     for (int j = 0; j < T; ++j) {
         const float dsr = ds[i * ld + j], dsc = ds[j * ld + i], pc = ps[j * ld + i];     // row (query i), columns (key i)
         float kr[CS], qr[CS], gr[CS];
-        mha_ld<CS>(ks + j * DH + w * CS, kr);
-        mha_ld<CS>(qs + j * DH + w * CS, qr);
-        mha_ld<CS>(gs + j * DH + w * CS, gr);
+        row_ld<CS>(ks + j * DH + w * CS, kr);
+        row_ld<CS>(qs + j * DH + w * CS, qr);
+        row_ld<CS>(gs + j * DH + w * CS, gr);
 #pragma unroll
         for (int e = 0; e < CS; ++e) {
             dq[e] += dsr * kr[e];
@@ -671,9 +669,9 @@ constexpr int kLnMaxD = 1024;
 
 static int launch_ln_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* y, float* mean,
                          float* rstd, int B, int D, int T, float eps, const DropSpec& spec, int nparts, size_t pstride,
-                         const float* xbias, float* xsum, hipStream_t st) {
+                         const float* xbias, float* xsum, float* vsum, hipStream_t st) {
 #define DYNMM_LN_F(NP) hipLaunchKernelGGL((ln_fwd_kernel<NP>), dim3(ceil_div(B * T, kLnTok)), dim3(256), 0, st, x, res, gamma, beta, \
-                                          y, mean, rstd, B, D, T, eps, spec, nparts, pstride, xbias, xsum)
+                                          y, mean, rstd, B, D, T, eps, spec, nparts, pstride, xbias, xsum, vsum)
     DYNMM_LN_DISPATCH(D, DYNMM_LN_F);
 #undef DYNMM_LN_F
     DYNMM_LAUNCH_CHECK();
@@ -686,7 +684,8 @@ extern "C" int dynmm_layernorm_drop_fwd(const float* x, const float* res, const 
     (void)hipGetLastError();
     if (!x || !gamma || !beta || !y || B <= 0 || D <= 0 || T <= 0 || !drop_ok(drop)) return DYNMM_EINVAL;
     if (D > kLnMaxD) return DYNMM_EUNSUPPORTED;
-    return launch_ln_fwd(x, res, gamma, beta, y, mean, rstd, B, D, T, eps, drop_spec(drop), 1, (size_t)0, nullptr, nullptr, ST);
+    return launch_ln_fwd(x, res, gamma, beta, y, mean, rstd, B, D, T, eps, drop_spec(drop), 1, (size_t)0, nullptr, nullptr,
+                         nullptr, ST);
 }
 
 extern "C" int dynmm_layernorm_parts_fwd(const float* parts, int nparts, const float* xbias, float* xsum, const float* res,
@@ -696,7 +695,7 @@ extern "C" int dynmm_layernorm_parts_fwd(const float* parts, int nparts, const f
     if (!parts || nparts <= 0 || !xsum || !gamma || !beta || !y || B <= 0 || D <= 0 || T <= 0 || !drop_ok(drop)) return DYNMM_EINVAL;
     if (D > kLnMaxD) return DYNMM_EUNSUPPORTED;
     return launch_ln_fwd(parts, res, gamma, beta, y, mean, rstd, B, D, T, eps, drop_spec(drop), nparts, (size_t)B * D * T,
-                         xbias, xsum, ST);
+                         xbias, xsum, nullptr, ST);
 }
 
 extern "C" int dynmm_layernorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* y,
@@ -704,9 +703,42 @@ extern "C" int dynmm_layernorm_fwd(const float* x, const float* res, const float
     return dynmm_layernorm_drop_fwd(x, res, gamma, beta, y, mean, rstd, B, D, T, eps, nullptr, stream);
 }
 
+// s = res + dropout(x) (x optional) and y = LayerNorm_D(s) in one launch, both returned; gamma == nullptr: the sum alone
+extern "C" int dynmm_prenorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* sum, float* y,
+                                 float* mean, float* rstd, int B, int D, int T, float eps, const dynmm_dropout* drop,
+                                 void* stream) {
+    (void)hipGetLastError();
+    if (!res || B <= 0 || D <= 0 || T <= 0 || !drop_ok(drop)) return DYNMM_EINVAL;
+    if (gamma ? (!beta || !y || !mean || !rstd) : (!sum || !x)) return DYNMM_EINVAL;
+    if (D > kLnMaxD) return DYNMM_EUNSUPPORTED;
+    return launch_ln_fwd(x, res, gamma, beta, y, mean, rstd, B, D, T, eps, drop_spec(drop), 1, (size_t)0, nullptr, nullptr, sum,
+                         ST);
+}
+
 extern "C" size_t dynmm_layernorm_bwd_workspace_bytes(int B, int D, int T) {
     if (B <= 0 || D <= 0 || T <= 0) return 0;
     return (size_t)ceil_div(B * T, kLnTok) * 2 * D * sizeof(float);
+}
+
+extern "C" size_t dynmm_prenorm_bwd_workspace_bytes(int B, int D, int T) { return dynmm_layernorm_bwd_workspace_bytes(B, D, T); }
+
+// the input-gradient pass and, with `part` (the workspace), the ordered reduction of its per-workgroup parameter sums
+template <bool SUMMED>
+static int launch_ln_bwd(const float* g, const float* gs, const float* x, const float* res, const float* gamma, const float* mean,
+                         const float* rstd, float* dx, float* dres, float* part, float* dgamma, float* dbeta, int accumulate,
+                         int B, int D, int T, const DropSpec& spec, hipStream_t st) {
+    const int nblk = ceil_div(B * T, kLnTok);
+#define DYNMM_LN_B(NP) hipLaunchKernelGGL((ln_bwd_dx_kernel<NP, SUMMED>), dim3(nblk), dim3(256), 0, st, g, x, res, gamma, mean, rstd, \
+                                          dx, dres, part, B, D, T, spec, gs)
+    DYNMM_LN_DISPATCH(D, DYNMM_LN_B);
+#undef DYNMM_LN_B
+    DYNMM_LAUNCH_CHECK();
+    if (part) {
+        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3(ceil_div(2 * D, 4)), dim3(256), 0, st, part, nblk, D, dgamma, dbeta,
+                           accumulate ? 1 : 0);
+        DYNMM_LAUNCH_CHECK();
+    }
+    return DYNMM_OK;
 }
 
 // workspace (optional, dynmm_layernorm_bwd_workspace_bytes): the parameter gradients come out of the input-gradient pass
@@ -722,23 +754,30 @@ extern "C" int dynmm_layernorm_drop_bwd_ws(const float* g, const float* x, const
     const bool fused = params && workspace && workspace_bytes >= dynmm_layernorm_bwd_workspace_bytes(B, D, T);
     if (workspace && params && !fused) return DYNMM_EINVAL;
     const DropSpec spec = drop_spec(drop);
-    const int nblk = ceil_div(B * T, kLnTok);
     if (dx || dres || fused) {
-        float* part = fused ? workspace : nullptr;
-#define DYNMM_LN_B(NP) hipLaunchKernelGGL((ln_bwd_dx_kernel<NP>), dim3(nblk), dim3(256), 0, ST, g, x, res, gamma, mean, rstd, dx, dres, \
-                                          part, B, D, T, spec)
-        DYNMM_LN_DISPATCH(D, DYNMM_LN_B);
-#undef DYNMM_LN_B
-        DYNMM_LAUNCH_CHECK();
+        const int err = launch_ln_bwd<false>(g, nullptr, x, res, gamma, mean, rstd, dx, dres, fused ? workspace : nullptr, dgamma,
+                                             dbeta, 0, B, D, T, spec, ST);
+        if (err != DYNMM_OK) return err;
     }
-    if (fused) {
-        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3(ceil_div(2 * D, 4)), dim3(256), 0, ST, workspace, nblk, D, dgamma, dbeta);
-        DYNMM_LAUNCH_CHECK();
-    } else if (params) {
+    if (params && !fused) {
         hipLaunchKernelGGL(ln_bwd_param_kernel, dim3(D), dim3(256), 0, ST, g, x, res, mean, rstd, dgamma, dbeta, B, D, T, spec);
         DYNMM_LAUNCH_CHECK();
     }
     return DYNMM_OK;
+}
+
+// the pre-norm layer's backward: ds = LayerNorm backward of gy + gs; dres = ds, dx = ds keep (`sum`: dynmm_prenorm_fwd's)
+extern "C" int dynmm_prenorm_bwd(const float* gy, const float* gs, const float* sum, const float* gamma, const float* mean,
+                                 const float* rstd, float* dx, float* dres, float* dgamma, float* dbeta, int B, int D, int T,
+                                 const dynmm_dropout* drop, int accumulate, float* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    (void)hipGetLastError();
+    if (!gy || !sum || !gamma || !mean || !rstd || B <= 0 || D <= 0 || T <= 0 || !drop_ok(drop)) return DYNMM_EINVAL;
+    if ((dgamma == nullptr) != (dbeta == nullptr)) return DYNMM_EINVAL;
+    if (dgamma && (!workspace || workspace_bytes < dynmm_prenorm_bwd_workspace_bytes(B, D, T))) return DYNMM_EWORKSPACE;
+    if (D > kLnMaxD) return DYNMM_EUNSUPPORTED;
+    return launch_ln_bwd<true>(gy, gs, sum, nullptr, gamma, mean, rstd, dx, dres, dgamma ? workspace : nullptr, dgamma, dbeta,
+                               accumulate, B, D, T, drop_spec(drop), ST);
 }
 
 extern "C" int dynmm_layernorm_drop_bwd(const float* g, const float* x, const float* res, const float* gamma,

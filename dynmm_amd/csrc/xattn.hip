@@ -1,10 +1,9 @@
 // MULT (MultiBench fusions.mult.MULTModel, affect_mm.py --fusion 4): what its pre-norm cross-modal transformers need beside the
 // GEMMs (every Linear / Conv1d(k=1) stays a 1x1 convolution on the implicit-GEMM kernels):
 //   * masked cross-modal attention with separate query and key lengths, forward + backward (dynmm_xattn_*),
-//   * the embedding dropout(scale x + pos(x)) with the padding rule, one or two dropout sites per launch (dynmm_posembed_*),
-//   * the pre-norm layer's `r + dropout(x)` fused with the LayerNorm that follows it (dynmm_prenorm_*): the launch returns the
-//     sum AND its normalisation.
-// DESIGN.md section 7m.
+//   * the embedding dropout(scale x + pos(x)) with the padding rule, one or two dropout sites per launch (dynmm_posembed_*).
+// The pre-norm layer's `r + dropout(x)` fused with the LayerNorm that follows it (dynmm_prenorm_*) runs on seq.hip's LayerNorm
+// kernels.  DESIGN.md section 7m.
 #include "common.h"
 #include "dropout.h"
 
@@ -12,20 +11,6 @@ namespace dynmm {
 
 constexpr int kXaMaxT = 64;
 constexpr int kXaMaxDh = 32;
-
-template <int N>
-__device__ __forceinline__ void xa_ld(const float* __restrict__ p, float r[N]) {       // p: aligned to the widest unit used
-    if constexpr (N % 4 == 0) {
-#pragma unroll
-        for (int q = 0; q < N / 4; ++q) {
-            const float4 t = reinterpret_cast<const float4*>(p)[q];
-            r[4 * q] = t.x; r[4 * q + 1] = t.y; r[4 * q + 2] = t.z; r[4 * q + 3] = t.w;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < N; ++q) r[q] = p[q];
-    }
-}
 
 // q . k as an unevaluated sum hi + lo of two floats (TwoProd / TwoSum, Ogita-Rump-Oishi Dot2: fp32 operations only, about twice
 // the working precision).  A score of magnitude 1e3 rounded to one float carries 6e-5 into the exponent, and the few rows whose two
@@ -103,7 +88,7 @@ __global__ void __launch_bounds__(64) xattn_fwd_kernel(const float* __restrict__
     float mxh = -INFINITY, mxl = 0.f;
     for (int j = 0; j < jmax; ++j) {
         float kr[DH], hi, lo;
-        xa_ld<DH>(ks + j * DH, kr);
+        row_ld<DH>(ks + j * DH, kr);
         xa_dot2<DH>(qr, kr, hi, lo);
         if (hi > mxh) {
             mxh = hi;
@@ -122,7 +107,7 @@ __global__ void __launch_bounds__(64) xattn_fwd_kernel(const float* __restrict__
             const int j = j0 + e;
             if (j < jmax) {
                 float kr[DH], hi, lo;
-                xa_ld<DH>(ks + j * DH, kr);
+                row_ld<DH>(ks + j * DH, kr);
                 xa_dot2<DH>(qr, kr, hi, lo);
                 // (q . k_j - max) / sqrt(dh): the difference first, then the scale (torch scales q; the same function)
                 const float ex = expf(((hi - mxh) + (lo - mxl)) * scale);
@@ -130,7 +115,7 @@ __global__ void __launch_bounds__(64) xattn_fwd_kernel(const float* __restrict__
                 den += ex;
                 const float w = ex * kp[e];                          // dropout acts on the normalised probabilities: linear in ex
                 float vr[DH];
-                xa_ld<DH>(vs + j * DH, vr);
+                row_ld<DH>(vs + j * DH, vr);
 #pragma unroll
                 for (int c = 0; c < DH; ++c) o[c] += w * vr[c];
             }
@@ -215,7 +200,7 @@ __global__ void __launch_bounds__(64) xattn_bwd_kernel(const float* __restrict__
             const int j = j0 + e;
             if (j < jmax) {
                 float vr[DH];
-                xa_ld<DH>(bs + j * DH, vr);
+                row_ld<DH>(bs + j * DH, vr);
                 float sacc = 0.f;
 #pragma unroll
                 for (int c = 0; c < DH; ++c) sacc += gq[c] * vr[c];
@@ -235,7 +220,7 @@ __global__ void __launch_bounds__(64) xattn_bwd_kernel(const float* __restrict__
         dr[j] = dsv;
         pr[j] = ((kept >> j) & 1ull) ? pv * drop.inv : 0.f;
         float kr[DH];
-        xa_ld<DH>(as + j * DH, kr);
+        row_ld<DH>(as + j * DH, kr);
 #pragma unroll
         for (int c = 0; c < DH; ++c) dqa[c] += dsv * kr[c];
     }
@@ -267,8 +252,8 @@ __global__ void __launch_bounds__(64) xattn_bwd_kernel(const float* __restrict__
     for (int r = r0; r < Tq; ++r) {
         const float dsc = ds[r * ld + i], pc = ps[r * ld + i];
         float qr[DH], gr[DH];
-        xa_ld<DH>(as + r * DH, qr);
-        xa_ld<DH>(bs + r * DH, gr);
+        row_ld<DH>(as + r * DH, qr);
+        row_ld<DH>(bs + r * DH, gr);
 #pragma unroll
         for (int c = 0; c < DH; ++c) {
             dka[c] += dsc * qr[c];
@@ -345,187 +330,6 @@ __global__ void __launch_bounds__(256) posembed_bwd_kernel(const float* __restri
     for (int e = 0; e < 8; ++e) {
         const int c = c8 * 8 + e;
         if (c < E) dx[base + (size_t)c * T] = scale * (a[e] * k1[e] + (g2 ? c2[e] * k2[e] : 0.f));
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Pre-norm plumbing: s = res + dropout(x) (x optional) and y = LayerNorm_D(s) in one launch, both returned; gamma == nullptr:
-// the residual sum alone.  Thread layout and register cache of seq.hip's LayerNorm (16 tokens x 16 groups of 8 channels, NP
-// passes).  Backward: ds = LayerNorm backward of gy + gs (gs = the gradient that reaches the sum directly, optional);
-// dres = ds, dx = ds keep; per-workgroup parameter sums in `part`, added in a fixed order by pn_param_reduce_kernel.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int kPnTok = 16, kPnGrp = 16, kPnCh = 8;
-
-__device__ __forceinline__ float pn_group_sum(float v, float (*sh)[kPnTok], int tl, int grp) {
-    sh[grp][tl] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < kPnGrp; ++k) s += sh[k][tl];               // fixed order: deterministic
-    __syncthreads();
-    return s;
-}
-
-template <int NP>
-__global__ void __launch_bounds__(256) prenorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          float* __restrict__ sum, float* __restrict__ y,
-                                                          float* __restrict__ mean, float* __restrict__ rstd, int B, int D,
-                                                          int T, float eps, const DropSpec spec) {
-    __shared__ float sh[kPnGrp][kPnTok];
-    const DropState ds(spec);
-    const int tl = threadIdx.x & (kPnTok - 1), grp = threadIdx.x / kPnTok;
-    const int tok = blockIdx.x * kPnTok + tl;
-    const bool ok = tok < B * T;
-    const int b = ok ? tok / T : 0, t = ok ? tok - b * T : 0;
-    const size_t base = (size_t)b * D * T + t;
-    const float* gp = gamma ? gamma : res;                          // (clamped, in-range reads either way; unused without gamma)
-    const float* bp = gamma ? beta : res;
-    float v[NP][kPnCh], gm[NP][kPnCh], bt[NP][kPnCh];
-    float s = 0.f;
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp) {
-        const int c8 = pp * kPnGrp + grp;
-        float k[kPnCh], xv[kPnCh], rv[kPnCh];
-        ds.keep8(b, min(c8, (D - 1) / kPnCh), t, D, T, k);
-#pragma unroll
-        for (int e = 0; e < kPnCh; ++e) {                          // unconditional loads on clamped addresses, selected below
-            const int cc = min(c8 * kPnCh + e, D - 1);
-            const size_t i = base + (size_t)cc * T;
-            xv[e] = x ? x[i] : 0.f;
-            rv[e] = res[i];
-            gm[pp][e] = gp[gamma ? cc : 0];
-            bt[pp][e] = bp[gamma ? cc : 0];
-        }
-#pragma unroll
-        for (int e = 0; e < kPnCh; ++e) {
-            const int c = c8 * kPnCh + e;
-            const bool valid = ok && c < D;
-            v[pp][e] = valid ? xv[e] * k[e] + rv[e] : 0.f;
-            s += v[pp][e];
-            if (valid && sum) sum[base + (size_t)c * T] = v[pp][e];
-        }
-    }
-    if (!gamma) return;                                             // (uniform over the launch)
-    const float mu = pn_group_sum(s, sh, tl, grp) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-        for (int e = 0; e < kPnCh; ++e)
-            if (ok && (pp * kPnGrp + grp) * kPnCh + e < D) {
-                const float d = v[pp][e] - mu;
-                q += d * d;
-            }
-    const float rs = rsqrtf(pn_group_sum(q, sh, tl, grp) / (float)D + eps);
-    if (!ok) return;
-    if (grp == 0) {
-        mean[tok] = mu;
-        rstd[tok] = rs;
-    }
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-        for (int e = 0; e < kPnCh; ++e) {
-            const int c = (pp * kPnGrp + grp) * kPnCh + e;
-            if (c < D) y[base + (size_t)c * T] = (v[pp][e] - mu) * rs * gm[pp][e] + bt[pp][e];
-        }
-}
-
-template <int NP>
-__global__ void __launch_bounds__(256) prenorm_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ gs,
-                                                          const float* __restrict__ sum, const float* __restrict__ gamma,
-                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          float* __restrict__ dx, float* __restrict__ dres,
-                                                          float* __restrict__ part, int B, int D, int T,
-                                                          const DropSpec spec) {
-    __shared__ float sh[kPnGrp][kPnTok];
-    const DropState ds(spec);
-    const int tl = threadIdx.x & (kPnTok - 1), grp = threadIdx.x / kPnTok;
-    const int tok = blockIdx.x * kPnTok + tl;
-    const bool ok = tok < B * T;
-    const int b = ok ? tok / T : 0, t = ok ? tok - b * T : 0;
-    const size_t base = (size_t)b * D * T + t;
-    const float mu = ok ? mean[tok] : 0.f, rs = ok ? rstd[tok] : 0.f;
-    float gv[NP][kPnCh], xh[NP][kPnCh], kk[NP][kPnCh], gm[NP][kPnCh], sv[NP][kPnCh];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp) {
-        const int c8 = pp * kPnGrp + grp;
-        ds.keep8(b, min(c8, (D - 1) / kPnCh), t, D, T, kk[pp]);
-        float xv[kPnCh];
-#pragma unroll
-        for (int e = 0; e < kPnCh; ++e) {
-            const int cc = min(c8 * kPnCh + e, D - 1);
-            const size_t i = base + (size_t)cc * T;
-            gv[pp][e] = gy[i];
-            sv[pp][e] = gs ? gs[i] : 0.f;
-            xv[e] = sum[i];
-            gm[pp][e] = gamma[cc];
-        }
-#pragma unroll
-        for (int e = 0; e < kPnCh; ++e) {
-            const bool valid = ok && c8 * kPnCh + e < D;
-            gv[pp][e] = valid ? gv[pp][e] : 0.f;
-            xh[pp][e] = valid ? (xv[e] - mu) * rs : 0.f;
-            const float gg = gv[pp][e] * gm[pp][e];
-            s1 += gg;
-            s2 += gg * xh[pp][e];
-        }
-    }
-    s1 = pn_group_sum(s1, sh, tl, grp) / (float)D;
-    s2 = pn_group_sum(s2, sh, tl, grp) / (float)D;
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-        for (int e = 0; e < kPnCh; ++e) {
-            const int c = (pp * kPnGrp + grp) * kPnCh + e;
-            if (ok && c < D) {
-                const size_t i = base + (size_t)c * T;
-                const float dv = rs * (gv[pp][e] * gm[pp][e] - s1 - xh[pp][e] * s2) + sv[pp][e];
-                if (dres) dres[i] = dv;
-                if (dx) dx[i] = dv * kk[pp][e];
-            }
-        }
-    if (part) {
-        // the 16 tokens of a channel sit in the 16 lanes of one row of the wave: xor-butterfly inside the row
-        float* pr = part + (size_t)blockIdx.x * 2 * D;
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-            for (int e = 0; e < kPnCh; ++e) {
-                float a = gv[pp][e] * xh[pp][e], bsum = gv[pp][e];
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) {
-                    a += __shfl_xor(a, o, 16);
-                    bsum += __shfl_xor(bsum, o, 16);
-                }
-                const int c = (pp * kPnGrp + grp) * kPnCh + e;
-                if (tl == 0 && c < D) {
-                    pr[c] = a;
-                    pr[D + c] = bsum;
-                }
-            }
-    }
-}
-
-// dgamma[c], dbeta[c] = the workgroups' rows of `part` added in a fixed order: one wave per column, lane = a 64-way split of rows
-// `accumulate`: the sums are ADDED to dgamma / dbeta (a LayerNorm applied to several inputs in one step: the launches of one stream
-// run in order, one thread owns a column, so the result is still a fixed-order sum).
-__global__ void __launch_bounds__(256) pn_param_reduce_kernel(const float* __restrict__ part, int nrows, int D,
-                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                              int accumulate) {
-    const int sp = threadIdx.x & 63;
-    const int col = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (col >= 2 * D) return;
-    const int per = (nrows + 63) / 64;
-    const int r0 = min(nrows, sp * per), r1 = min(nrows, (sp + 1) * per);
-    float s = 0.f;
-    for (int r = r0; r < r1; ++r) s += part[(size_t)r * 2 * D + col];
-    s = wave_reduce_sum<float>(s);
-    if (sp == 0) {
-        float* dst = col < D ? dgamma + col : dbeta + (col - D);
-        *dst = accumulate ? *dst + s : s;
     }
 }
 
@@ -621,60 +425,5 @@ extern "C" int dynmm_posembed_bwd(const float* g1, const float* g2, float* dx, i
     hipLaunchKernelGGL(posembed_bwd_kernel, dim3((unsigned)ceil_div_sz(n, 256)), dim3(256), 0, ST, g1, g2, dx, B, E, T, scale,
                        drop_spec(drop1), drop_spec(drop2));
     DYNMM_LAUNCH_CHECK();
-    return DYNMM_OK;
-}
-
-#define DYNMM_PN_DISPATCH(D, CALL)                 \
-    do {                                           \
-        if ((D) <= 128) { CALL(1); }               \
-        else if ((D) <= 256) { CALL(2); }          \
-        else if ((D) <= 512) { CALL(4); }          \
-        else { CALL(8); }                          \
-    } while (0)
-constexpr int kPnMaxD = 1024;
-
-extern "C" int dynmm_prenorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* sum, float* y,
-                                 float* mean, float* rstd, int B, int D, int T, float eps, const dynmm_dropout* drop,
-                                 void* stream) {
-    (void)hipGetLastError();
-    if (!res || B <= 0 || D <= 0 || T <= 0 || !drop_ok(drop)) return DYNMM_EINVAL;
-    if (gamma ? (!beta || !y || !mean || !rstd) : (!sum || !x)) return DYNMM_EINVAL;
-    if (D > kPnMaxD) return DYNMM_EUNSUPPORTED;
-    const DropSpec spec = drop_spec(drop);
-#define DYNMM_PN_F(NP) hipLaunchKernelGGL((prenorm_fwd_kernel<NP>), dim3(ceil_div(B * T, kPnTok)), dim3(256), 0, ST, x, res, gamma, \
-                                          beta, sum, y, mean, rstd, B, D, T, eps, spec)
-    DYNMM_PN_DISPATCH(D, DYNMM_PN_F);
-#undef DYNMM_PN_F
-    DYNMM_LAUNCH_CHECK();
-    return DYNMM_OK;
-}
-
-extern "C" size_t dynmm_prenorm_bwd_workspace_bytes(int B, int D, int T) {
-    if (B <= 0 || D <= 0 || T <= 0) return 0;
-    return (size_t)ceil_div(B * T, kPnTok) * 2 * D * sizeof(float);
-}
-
-extern "C" int dynmm_prenorm_bwd(const float* gy, const float* gs, const float* sum, const float* gamma, const float* mean,
-                                 const float* rstd, float* dx, float* dres, float* dgamma, float* dbeta, int B, int D, int T,
-                                 const dynmm_dropout* drop, int accumulate, float* workspace, size_t workspace_bytes,
-                                 void* stream) {
-    (void)hipGetLastError();
-    if (!gy || !sum || !gamma || !mean || !rstd || B <= 0 || D <= 0 || T <= 0 || !drop_ok(drop)) return DYNMM_EINVAL;
-    if ((dgamma == nullptr) != (dbeta == nullptr)) return DYNMM_EINVAL;
-    if (dgamma && (!workspace || workspace_bytes < dynmm_prenorm_bwd_workspace_bytes(B, D, T))) return DYNMM_EWORKSPACE;
-    if (D > kPnMaxD) return DYNMM_EUNSUPPORTED;
-    const DropSpec spec = drop_spec(drop);
-    const int nblk = ceil_div(B * T, kPnTok);
-    float* part = dgamma ? workspace : nullptr;
-#define DYNMM_PN_B(NP) hipLaunchKernelGGL((prenorm_bwd_kernel<NP>), dim3(nblk), dim3(256), 0, ST, gy, gs, sum, gamma, mean, rstd, dx, \
-                                          dres, part, B, D, T, spec)
-    DYNMM_PN_DISPATCH(D, DYNMM_PN_B);
-#undef DYNMM_PN_B
-    DYNMM_LAUNCH_CHECK();
-    if (dgamma) {
-        hipLaunchKernelGGL(pn_param_reduce_kernel, dim3(ceil_div(2 * D, 4)), dim3(256), 0, ST, workspace, nblk, D, dgamma, dbeta,
-                           accumulate ? 1 : 0);
-        DYNMM_LAUNCH_CHECK();
-    }
     return DYNMM_OK;
 }

@@ -2,8 +2,8 @@
 
 Activations are [B, D, T] fp32 (the layout the reference feeds its Conv1d after `x.permute([0, 2, 1])`); every Linear
 / Conv1d(k=1) is `linear_bdt` = the implicit-GEMM MFMA convolution of ops.conv2d with H = 1, W = T.  The kernels
-added for this path live in csrc/seq.hip (attention for head dimensions above 32: csrc/attn.hip; MULT's masked cross-modal
-attention, embedding and pre-norm plumbing: csrc/xattn.hip).  As everywhere in dynmm_amd there is no CPU / eager fallback.
+added for this path live in csrc/seq.hip (with MULT's pre-norm plumbing; attention for head dimensions above 32: csrc/attn.hip;
+MULT's masked cross-modal attention and embedding: csrc/xattn.hip).  As everywhere in dynmm_amd there is no CPU / eager fallback.
 """
 import ctypes as C
 import itertools
@@ -87,6 +87,11 @@ def _drop_arg(d):
     return C.byref(d.desc()) if d is not None and d.p > 0 else None
 
 
+def _make_drop(d, shape, device):
+    """the Drop of one call from d = (p, site, name); None for d None or p == 0"""
+    return Drop(d[0], d[1], d[2], shape, device) if d is not None and d[0] > 0 else None
+
+
 class _DropoutBDT(Function):
     @staticmethod
     def forward(ctx, x, drop):
@@ -136,6 +141,21 @@ def _ln_ws(lib, like, B, D, T, params):
     return torch.empty(nb // 4, device=like.device, dtype=torch.float32), nb
 
 
+def _ln_stats(like, B, T):
+    """(mean, rstd) of B * T tokens, to be filled by a LayerNorm forward"""
+    return tuple(torch.empty(B * T, device=like.device, dtype=torch.float32) for _ in range(2))
+
+
+def _ln_grad_bufs(like, need_x, need_res, drop, dres=None):
+    """(dx, dres, gx) for the backward of dropout(x) + res: without dropout the two branches of the sum receive the same tensor
+    (dres, allocated unless given; dx is None); with it x gets its keep factor on top (dx).  gx: x's gradient, if needed."""
+    dropping = drop is not None and drop.p > 0
+    if dres is None and (need_res or (need_x and not dropping)):
+        dres = torch.empty_like(like)
+    dx = torch.empty_like(like) if (need_x and dropping) else None
+    return dx, dres, ((dx if dropping else dres) if need_x else None)
+
+
 class _LayerNormBDT(Function):
     @staticmethod
     def forward(ctx, x, res, gamma, beta, eps, drop=None, res_link=None):
@@ -144,8 +164,7 @@ class _LayerNormBDT(Function):
         x, res, gamma, beta = _chk(x, 'x'), _chk(res, 'res'), _chk(gamma, 'gamma'), _chk(beta, 'beta')
         B, D, T = x.shape
         y = torch.empty_like(x)
-        mean = torch.empty(B * T, device=x.device, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
+        mean, rstd = _ln_stats(x, B, T)
         L.check(lib.dynmm_layernorm_drop_fwd(_p(x), _p(res), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), B, D, T,
                                              float(eps), _drop_arg(drop), _stream()), 'layernorm_fwd')
         ctx.drop = drop
@@ -161,10 +180,7 @@ class _LayerNormBDT(Function):
         B, D, T = x.shape
         need_x = ctx.needs_input_grad[0]
         need_res = res is not None and ctx.needs_input_grad[1]
-        dropping = ctx.drop is not None and ctx.drop.p > 0
-        # without dropout the two branches of the sum receive the same tensor; with it x gets its keep factor on top
-        dres = torch.empty_like(x) if (need_res or (need_x and not dropping)) else None
-        dx = torch.empty_like(x) if (need_x and dropping) else None
+        dx, dres, gx = _ln_grad_bufs(x, need_x, need_res, ctx.drop)
         dg = dg_ret = db = db_ret = None
         if ctx.needs_input_grad[2]:
             dg, dg_ret = _grad_dst(ctx.g_param)
@@ -178,14 +194,14 @@ class _LayerNormBDT(Function):
             # accumulation pass by autograd
             ctx.res_link.dres = dres.reshape(B, D, 1, T)
             need_res = False
-        return ((dx if dropping else dres) if need_x else None), (dres if need_res else None), dg_ret, db_ret, None, None, None
+        return gx, (dres if need_res else None), dg_ret, db_ret, None, None, None
 
 
 def layernorm_bdt(x, gamma, beta, eps=1e-5, residual=None, drop=None, res_link=None):
     """LayerNorm over D of (dropout(x) + residual), x [B, D, T]; drop = (p, site, name) or None.  res_link: an ops.GradLink
     shared with the linear_bdt that also consumes `residual` and whose output this layer's x descends from (so its backward
     runs after this one): the residual branch's gradient is added there instead of by autograd."""
-    d = Drop(drop[0], drop[1], drop[2], x.shape, x.device) if drop is not None and drop[0] > 0 else None
+    d = _make_drop(drop, x.shape, x.device)
     if not (res_link is not None and residual is not None and torch.is_grad_enabled() and residual.requires_grad):
         res_link = None
     return _LayerNormBDT.apply(x, residual, gamma, beta, eps, d, res_link)
@@ -240,8 +256,7 @@ class _FFNBlock(Function):
         L.check(lib.dynmm_ffn_fwd(_p(h), _p(w1), _p(b1), _p(w2), _p(hidden), _p(parts), B, D, T, F, ns, _drop_arg(drop_f),
                                   _stream()), 'ffn_fwd')
         y, xsum = torch.empty_like(h), torch.empty_like(h)
-        mean = torch.empty(B * T, device=h.device, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
+        mean, rstd = _ln_stats(h, B, T)
         L.check(lib.dynmm_layernorm_parts_fwd(_p(parts), ns, _p(b2), _p(xsum), _p(h), _p(gamma), _p(beta), _p(y), _p(mean),
                                               _p(rstd), B, D, T, float(eps), _drop_arg(drop2), _stream()), 'layernorm_parts_fwd')
         ctx.drop_f, ctx.drop2, ctx.ns = drop_f, drop2, ns
@@ -258,19 +273,16 @@ class _FFNBlock(Function):
         B, D, T = h.shape
         F, ns = w1.shape[0], ctx.ns
         st = _stream()
-        dropping2 = ctx.drop2 is not None and ctx.drop2.p > 0
         # slab ns = the residual branch's gradient, slabs 0 .. ns-1 = the feed-forward branch's partial sums
         slabs = torch.empty((ns + 1, B, D, T), device=h.device, dtype=torch.float32)
-        dres = slabs[ns]
-        dout = torch.empty_like(h) if dropping2 else dres
+        dx, dres, dout = _ln_grad_bufs(h, True, True, ctx.drop2, dres=slabs[ns])
         dg = dg_ret = db = db_ret = None
         if ctx.needs_input_grad[5]:
             dg, dg_ret = _grad_dst(pgamma)
             db, db_ret = _grad_dst(pbeta)
         ws, nb = _ln_ws(lib, g, B, D, T, dg is not None)
-        L.check(lib.dynmm_layernorm_drop_bwd_ws(_p(g), _p(xsum), _p(h), _p(gamma), _p(mean), _p(rstd),
-                                                _p(dout) if dropping2 else None, _p(dres), _p(dg), _p(db), B, D, T,
-                                                _drop_arg(ctx.drop2), _p(ws), nb, st), 'layernorm_bwd')
+        L.check(lib.dynmm_layernorm_drop_bwd_ws(_p(g), _p(xsum), _p(h), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dg),
+                                                _p(db), B, D, T, _drop_arg(ctx.drop2), _p(ws), nb, st), 'layernorm_bwd')
         _grads_enqueued()
         dhid = torch.empty_like(hidden)
         pf = ctx.drop_f.p if ctx.drop_f is not None else 0.0
@@ -294,8 +306,7 @@ def ffn_block(h, layer, drop_f, drop2):
     """norm2(h + dropout2(linear2(dropout(relu(linear1(h)))))) of an nn.TransformerEncoderLayer; drop_* = (p, site, name)."""
     B, D, T = h.shape
     F = layer.linear1.weight.shape[0]
-    df = Drop(drop_f[0], drop_f[1], drop_f[2], (B, F, T), h.device) if drop_f[0] > 0 else None
-    d2 = Drop(drop2[0], drop2[1], drop2[2], h.shape, h.device) if drop2[0] > 0 else None
+    df, d2 = _make_drop(drop_f, (B, F, T), h.device), _make_drop(drop2, h.shape, h.device)
     return _FFNBlock.apply(h, layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias,
                            layer.norm2.weight, layer.norm2.bias, layer.norm2.eps, df, d2)
 
@@ -514,9 +525,7 @@ MHA_CORE_MAX_DH = 32     # csrc/seq.hip: kSeqMaxDh
 
 def _probs_drop(qkv, heads, drop):
     """the Drop of the [B*heads, T, T] attention probabilities; drop = (p, site, name) or None"""
-    if drop is None or not drop[0] > 0:
-        return None
-    return Drop(drop[0], drop[1], drop[2], (qkv.shape[0] * heads, qkv.shape[2], qkv.shape[2]), qkv.device)
+    return _make_drop(drop, (qkv.shape[0] * heads, qkv.shape[2], qkv.shape[2]), qkv.device)
 
 
 def mha_core(qkv, heads, drop=None):
@@ -539,7 +548,7 @@ def attention(qkv, heads, drop=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# MULT (MultiBench fusions.mult.MULTModel): masked cross-modal attention, the embedding and the pre-norm plumbing, csrc/xattn.hip
+# MULT (MultiBench fusions.mult.MULTModel): cross-modal attention and embedding (csrc/xattn.hip), pre-norm plumbing (csrc/seq.hip)
 # ---------------------------------------------------------------------------------------------------------------
 XATTN_MAX_DH, XATTN_MAX_T = 32, 64       # csrc/xattn.hip: kXaMaxDh, kXaMaxT
 
@@ -622,25 +631,20 @@ class _PackedAttention(Function):
         return dqkv, None, None, None
 
 
-def _xattn_drop(drop, B, heads, Tq, Tk, device):
-    if drop is None or not drop[0] > 0:
-        return None
-    return Drop(drop[0], drop[1], drop[2], (B * heads, Tq, Tk), device)
-
-
 def cross_attention(q, k, v, heads, causal, drop=None):
     """dropout(softmax(q k^T / sqrt(dh) + mask)) v per head for q [B, D, Tq], k and v [B, D, Tk] -> [B, D, Tq].  causal: key j is
     visible to query i iff j <= i + |Tk - Tq| (MULT's future mask, torch.triu(-inf, 1 + |Tk - Tq|)).  q, k, v may be channel
     slices of one packed [B, 3D, T] tensor (no copy; `packed_attention` also returns their gradient as one tensor).
     drop = (p, site, name) or None: dropout on the [B*heads, Tq, Tk] probabilities.  Head dimensions up to 32, lengths up to 64
     (csrc/xattn.hip)."""
-    return _CrossAttention.apply(q, k, v, heads, causal, _xattn_drop(drop, q.shape[0], heads, q.shape[2], k.shape[2], q.device))
+    return _CrossAttention.apply(q, k, v, heads, causal,
+                                 _make_drop(drop, (q.shape[0] * heads, q.shape[2], k.shape[2]), q.device))
 
 
 def packed_attention(qkv, heads, causal, drop=None):
     """cross_attention on qkv [B, 3D, T] (q | k | v along channels, an in_proj's output): masked self-attention."""
     B, _, T = qkv.shape
-    return _PackedAttention.apply(qkv, heads, causal, _xattn_drop(drop, B, heads, T, T, qkv.device))
+    return _PackedAttention.apply(qkv, heads, causal, _make_drop(drop, (B * heads, T, T), qkv.device))
 
 
 class _PosEmbed(Function):
@@ -678,8 +682,8 @@ def pos_embed(x, pos, scale, drop=None, drop2=None):
     time steps whose x[b, 0, t] is exactly 0 (padding).  drop / drop2 = (p, site, name): with drop2 the launch returns two outputs
     with dropout decisions of their own (the key and the value embedding of one source)."""
     pos = _operand('pos_embed', pos, 'pos', (x.shape[1], x.shape[2]))
-    mk = lambda d: Drop(d[0], d[1], d[2], x.shape, x.device) if d is not None and d[0] > 0 else None      # noqa: E731
-    return _PosEmbed.apply(x, pos, scale, mk(drop), mk(drop2), drop2 is not None)
+    return _PosEmbed.apply(x, pos, scale, _make_drop(drop, x.shape, x.device), _make_drop(drop2, x.shape, x.device),
+                           drop2 is not None)
 
 
 class _PreNorm(Function):
@@ -694,8 +698,7 @@ class _PreNorm(Function):
         B, D, T = res.shape
         y = torch.empty_like(res)
         s = torch.empty_like(res) if x is not None else None
-        mean = torch.empty(B * T, device=res.device, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
+        mean, rstd = _ln_stats(res, B, T)
         L.check(lib.dynmm_prenorm_fwd(_p(x), _p(res), _p(gamma), _p(beta), _p(s), _p(y), _p(mean), _p(rstd), B, D, T, float(eps),
                                       _drop_arg(drop), _stream()), 'prenorm_fwd')
         ctx.drop, ctx.direct, ctx.has_x = drop, direct, x is not None
@@ -716,11 +719,8 @@ class _PreNorm(Function):
             gy = torch.zeros_like(s)               # only the sum was used downstream (no model of this project does that)
         gy, gs = _chk(gy, 'grad'), _chk(gs, 'grad')
         need_res, need_x = ctx.needs_input_grad[0], ctx.has_x and ctx.needs_input_grad[1]
-        dropping = ctx.drop is not None and ctx.drop.p > 0
-        dres = torch.empty_like(s) if (need_res or (need_x and not dropping)) else None
-        dx = torch.empty_like(s) if (need_x and dropping) else None
-        dg = dg_ret = db = db_ret = ws = None
-        nb = 0
+        dx, dres, gx = _ln_grad_bufs(s, need_x, need_res, ctx.drop)
+        dg = dg_ret = db = db_ret = None
         acc = 0
         if ctx.needs_input_grad[2]:
             if ctx.direct or (ops._direct_ok(ctx.g_param) and ops._direct_ok(ctx.b_param)):
@@ -732,12 +732,11 @@ class _PreNorm(Function):
             else:
                 dg = dg_ret = torch.empty_like(gamma)
                 db = db_ret = torch.empty_like(gamma)
-            nb = lib.dynmm_prenorm_bwd_workspace_bytes(B, D, T)
-            ws = torch.empty(nb // 4, device=s.device, dtype=torch.float32)
+        ws, nb = _ln_ws(lib, s, B, D, T, dg is not None)
         L.check(lib.dynmm_prenorm_bwd(_p(gy), _p(gs), _p(s), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dg), _p(db), B,
                                       D, T, _drop_arg(ctx.drop), acc, _p(ws), nb, _stream()), 'prenorm_bwd')
         _grads_enqueued()
-        return (dres if need_res else None), ((dx if dropping else dres) if need_x else None), dg_ret, db_ret, None, None, None
+        return (dres if need_res else None), gx, dg_ret, db_ret, None, None, None
 
 
 def prenorm_bdt(res, gamma, beta, eps=1e-5, x=None, drop=None, shared=False):
@@ -746,12 +745,12 @@ def prenorm_bdt(res, gamma, beta, eps=1e-5, x=None, drop=None, shared=False):
     name) or None.  shared: this LayerNorm's parameters are applied to several inputs in one step (MULT's LN0 on query, key and
     value): inside a training step their gradients are ADDED to the parameter's gradient in place instead of overwriting it,
     otherwise they go back to autograd, which sums them."""
-    d = Drop(drop[0], drop[1], drop[2], x.shape, x.device) if x is not None and drop is not None and drop[0] > 0 else None
+    d = _make_drop(drop, x.shape, x.device) if x is not None else None
     return _PreNorm.apply(res, x, gamma, beta, eps, d, not shared)
 
 
 class _ResidualAdd(Function):
-    """res + x, [B, D, ...] (csrc/xattn.hip's pre-norm kernel without its LayerNorm)."""
+    """res + x, [B, D, ...] (csrc/seq.hip's LayerNorm forward without gamma: it returns after storing the sum)."""
 
     @staticmethod
     def forward(ctx, res, x):

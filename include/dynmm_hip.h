@@ -829,8 +829,8 @@ int dynmm_posembed_fwd(const float* x, const float* pos, float* y1, float* y2, i
                        const dynmm_dropout* drop1, const dynmm_dropout* drop2, void* stream);
 int dynmm_posembed_bwd(const float* g1, const float* g2, float* dx, int B, int E, int T, float scale,
                        const dynmm_dropout* drop1, const dynmm_dropout* drop2, void* stream);
-/* Pre-norm plumbing: sum = res + dropout(x) (x NULL: sum = res, nothing dropped) and y = LayerNorm over D of sum, [B, D, T], in one
- * launch; sum (optional when gamma is given) and y are both written; gamma NULL: the residual sum alone (x and sum required).
+/* Pre-norm plumbing (csrc/seq.hip, on the kernels of dynmm_layernorm_*): sum = res + dropout(x) (x NULL: sum = res, nothing
+ * dropped) and y = LayerNorm over D of sum, [B, D, T], in one launch; sum (optional when gamma is given) and y are both written; gamma NULL: the residual sum alone (x and sum required).
  * bwd: gy = the gradient of y, gs (optional) = the gradient that reaches sum directly; d = LayerNorm backward of gy at sum + gs;
  * dres (optional) = d, dx (optional) = d * keep; dgamma and dbeta (both or neither; then the workspace of
  * dynmm_prenorm_bwd_workspace_bytes is required, else DYNMM_EWORKSPACE) are OVERWRITTEN, or with accumulate != 0 ADDED TO (a

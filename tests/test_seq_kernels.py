@@ -503,6 +503,158 @@ def test_layernorm_refuses_more_than_1024_channels():
         S.layernorm_bdt(x, gamma, beta, EPS, residual=res)
 
 
+# the pre-norm layer on the same kernels (dynmm_prenorm_*, ops_seq.prenorm_bdt / residual_add)
+PN_DIMS = [7, 129, 300, 1001]                 # one D per pass count 1, 2, 4, 8, none a multiple of 8
+PN_TOKENS = [(1, 3), (3, 21)]                 # fewer than 16 tokens; not a multiple of 16
+PN_NAMES = ['sum', 'y', 'mean', 'rstd', 'dres', 'dx', 'dgamma', 'dbeta']
+
+
+def _pn_grads(res, x, gamma, beta, gy, gs, keep=None):
+    """(sum, y, mean, rstd, dres, dx, dgamma, dbeta) of sum = res + x * keep (x None: res), y = LayerNorm(sum); gy flows into y
+    and gs (optional) into sum."""
+    leaves = [t.requires_grad_(True) for t in (res, x, gamma, beta) if t is not None]
+    s = res if x is None else (x if keep is None else x * keep) + res
+    y, mean, rstd = ref_layernorm(s, None, gamma, beta, EPS)
+    gr = list(torch.autograd.grad([y] if gs is None else [y, s], leaves, [gy] if gs is None else [gy, gs]))
+    if x is None:
+        gr.insert(1, None)
+    return [s.detach(), y.detach(), mean.detach(), rstd.detach()] + gr
+
+
+def _pn_run(S, res, x, gamma, beta, gy, gs, drop=None):
+    """the same through prenorm_bdt; the leaves come back for their .grad"""
+    rc, xc, gc, bc = (None if t is None else _cu(t).requires_grad_(True) for t in (res, x, gamma, beta))
+    out = S.prenorm_bdt(rc, gc, bc, EPS, x=xc, drop=drop)
+    s, y = out if x is not None else (None, out)
+    mean, rstd = y.grad_fn.saved_tensors[2:4]
+    torch.autograd.backward([y] if gs is None else [y, s], [_cu(gy)] if gs is None else [_cu(gy), _cu(gs)])
+    return [s, y, mean, rstd, rc.grad, None if xc is None else xc.grad, gc.grad, bc.grad]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('D', PN_DIMS)
+def test_prenorm_matches_float64(D):
+    """prenorm_bdt on every pass count: without x, with x, with x and injected keep flags; gradients into both outputs and into
+    y alone.  Without dropout the sum is res + x to the bit; dropped elements of x receive exactly zero gradient."""
+    S = _S()
+    p = 0.3
+    fig = _Figures()
+    for B, T in PN_TOKENS:
+        x, res, gamma, beta, gy = _ln_inputs(B, D, T, True, 0.0, D * 100 + T)
+        gs_ = torch.randn(B, D, T, generator=_gen(D + T))
+        m = (torch.rand(B, D, T, generator=_gen(D + T + 1)) >= p)
+        keep = m.float() / (1 - p)
+        for form, xin, kp in (('nox', None, None), ('x', x, None), ('mask', x, keep)):
+            for gs in ((None,) if xin is None else (gs_, None)):
+                tag = f'pn D={D} B={B} T={T} {form} gs={int(gs is not None)}'
+                r64, r32 = _both(_pn_grads, (res, xin, gamma, beta, gy, gs, kp))
+                S.MASKS = _FixedMasks(res1=m.to(torch.uint8).cuda()) if kp is not None else None
+                try:
+                    got = _pn_run(S, res, xin, gamma, beta, gy, gs, drop=(p, 7, 'res1') if kp is not None else None)
+                    torch.cuda.synchronize()
+                finally:
+                    S.MASKS = None
+                for i, n in enumerate(PN_NAMES):
+                    if got[i] is not None:
+                        fig.check(f'{tag} {n}', got[i], r64[i], r32[i], LN_FWD if i < 4 else LN_BWD)
+                if form == 'x':
+                    assert torch.equal(got[0], _cu(res) + _cu(x)), tag
+                if form == 'mask':
+                    dx = got[5].cpu()
+                    assert bool((dx[~m] == 0).all()) and bool((dx[m] != 0).any()), tag
+    fig.done()
+
+
+@pytest.mark.gpu
+def test_prenorm_and_layernorm_give_the_same_bits():
+    """One kernel: on the same inputs and keep flags prenorm_bdt's y, mean and rstd are layernorm_bdt's."""
+    S = _S()
+    B, D, T, p = 3, 300, 21, 0.3
+    x, res, gamma, beta, _ = (_cu(t) for t in _ln_inputs(B, D, T, True, 0.0, 5))
+    m = (torch.rand(B, D, T, generator=_gen(6)) >= p).to(torch.uint8).cuda()
+    S.MASKS = _FixedMasks(res1=m)
+    try:
+        _, y_pn = S.prenorm_bdt(res.requires_grad_(True), gamma, beta, EPS, x=x, drop=(p, 7, 'res1'))
+        y_ln = S.layernorm_bdt(x.requires_grad_(True), gamma, beta, EPS, residual=res, drop=(p, 7, 'res1'))
+        torch.cuda.synchronize()
+    finally:
+        S.MASKS = None
+    assert torch.equal(y_pn, y_ln)
+    for a, b in zip(y_pn.grad_fn.saved_tensors[2:4], y_ln.grad_fn.saved_tensors[3:5]):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+def test_prenorm_bwd_accumulates_parameter_gradients():
+    """dynmm_prenorm_bwd with accumulate = 1 adds its sums to dgamma / dbeta: one float32 add per element on top of the
+    accumulate = 0 result.  69 workgroups: the reduction sees more than 64 rows."""
+    S = _S()
+    lib, st = S._lib(), S._stream()
+    B, D, T = 22, 129, 50
+    _, res, gamma, beta, gy = (_cu(t) for t in _ln_inputs(B, D, T, True, 0.0, 3))
+    y = torch.empty_like(res)
+    mean, rstd = torch.empty(B * T, device='cuda'), torch.empty(B * T, device='cuda')
+    assert lib.dynmm_prenorm_fwd(None, _ptr(res), _ptr(gamma), _ptr(beta), None, _ptr(y), _ptr(mean), _ptr(rstd), B, D, T, EPS,
+                                 None, st) == 0
+    nb = lib.dynmm_prenorm_bwd_workspace_bytes(B, D, T)
+    assert nb == -(-B * T // 16) * 2 * D * 4
+    ws = torch.empty(nb // 4, device='cuda')
+    pre = [torch.randn(D, generator=_gen(4 + i)).cuda() for i in range(2)]
+    out = {}
+    for acc in (0, 1):
+        dg, db = pre[0].clone(), pre[1].clone()
+        dres = torch.empty_like(res)
+        assert lib.dynmm_prenorm_bwd(_ptr(gy), None, _ptr(res), _ptr(gamma), _ptr(mean), _ptr(rstd), None, _ptr(dres), _ptr(dg),
+                                     _ptr(db), B, D, T, None, acc, _ptr(ws), nb, st) == 0
+        out[acc] = (dg, db, dres)
+    torch.cuda.synchronize()
+    assert torch.equal(out[1][0], pre[0] + out[0][0]) and torch.equal(out[1][1], pre[1] + out[0][1])
+    assert torch.equal(out[1][2], out[0][2]) and not torch.equal(out[0][0], pre[0])
+
+
+@pytest.mark.gpu
+def test_residual_add_is_exact():
+    S = _S()
+    g = _gen(11)
+    res, x, gy = (_cu(torch.randn(2, 1001, 9, generator=g)) for _ in range(3))
+    s = S.residual_add(res.requires_grad_(True), x.requires_grad_(True))
+    s.backward(gy)
+    assert torch.equal(s, res + x)
+    assert torch.equal(res.grad, gy) and torch.equal(x.grad, gy)
+
+
+@pytest.mark.gpu
+def test_prenorm_refusals_write_nothing():
+    S = _S()
+    from dynmm_amd import lib as L
+    lib, st = S._lib(), S._stream()
+
+    def call(B, D, T, beta_null=False, short=0):
+        """(forward code, backward code, outputs prefilled with 7.0)"""
+        x, res, gamma, beta, gy = (_cu(t) for t in _ln_inputs(B, D, T, True, 0.0, 1))
+        mean, rstd = torch.full((B * T,), 7.0, device='cuda'), torch.full((B * T,), 7.0, device='cuda')
+        big = [torch.full((B, D, T), 7.0, device='cuda') for _ in range(2)]
+        small = [torch.full((D,), 7.0, device='cuda') for _ in range(2)]
+        nb = lib.dynmm_prenorm_bwd_workspace_bytes(B, D, T)
+        ws = torch.full((nb // 4,), 7.0, device='cuda')
+        f = lib.dynmm_prenorm_fwd(_ptr(x), _ptr(res), _ptr(gamma), None if beta_null else _ptr(beta), _ptr(big[0]), _ptr(big[1]),
+                                  _ptr(mean), _ptr(rstd), B, D, T, EPS, None, st)
+        stats = [torch.zeros(B * T, device='cuda'), torch.ones(B * T, device='cuda')]
+        b = lib.dynmm_prenorm_bwd(_ptr(gy), _ptr(x), _ptr(res), _ptr(gamma), _ptr(stats[0]), _ptr(stats[1]), _ptr(big[0]),
+                                  _ptr(big[1]), _ptr(small[0]), _ptr(small[1]), B, D, T, None, 0, _ptr(ws), nb - short, st)
+        torch.cuda.synchronize()
+        return f, b, [mean, rstd, ws] + big + small
+
+    f, b, outs = call(2, 1025, 5)
+    assert f == L.DYNMM_EUNSUPPORTED and b == L.DYNMM_EUNSUPPORTED
+    assert all(bool((t == 7.0).all()) for t in outs)
+    f, b, outs = call(2, 129, 5, beta_null=True, short=1)
+    assert f == L.DYNMM_EINVAL and b == L.DYNMM_EWORKSPACE
+    assert all(bool((t == 7.0).all()) for t in outs)
+    with pytest.raises(L.DynmmHipError):
+        S.prenorm_bdt(torch.zeros(2, 1025, 5, device='cuda'), torch.ones(1025, device='cuda'), torch.zeros(1025, device='cuda'))
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # 2. attention core
 # ---------------------------------------------------------------------------------------------------------------
