@@ -5,6 +5,7 @@ every FLOP and every byte moved on the hot path is done by the kernels in libdyn
 functions require contiguous fp32 tensors on a HIP device and raise otherwise — there is no eager
 fallback.
 """
+import collections
 import contextlib
 import ctypes as C
 
@@ -123,6 +124,65 @@ def _wino(g, dgrad, x2=None, infer=False):
         # 1: stride-1 three-tap / 3x3 (Winograd); 2 (input gradient only): stride-2 three-tap (polyphase form of the same kernel)
         ok = _WINO_OK[key] = int(_lib().dynmm_conv2d_wino_supported(C.byref(g), int(bool(dgrad))))
     return ok
+
+
+# A pass of a convolution runs on ONE kernel family, its route, and reads ONE re-laid weight: the operand kind of that route
+_FWD_KIND = {'direct': 'fwd', 'wino': 'wino_fwd', 'wino2d': 'wino2d_fwd'}
+_DGRAD_KIND = {'direct': 'dgrad', 'wino': 'wino_dgrad', 'wino_s2': 'wino_dgrad_s2', 'wino43': 'wino43_dgrad',
+               'wino2d': 'wino2d_dgrad'}
+_WINO_F23 = ('wino', 'wino_s2')      # the input-gradient routes of csrc/conv_wino.hip's 1-D F(2,3) kernels
+
+
+def _fwd_route(g, x2, aligned, infer=False):
+    """kernel family of the forward pass.  aligned: x (16 bytes) and an epilogue operand (8) sit on the Winograd kernels' grid"""
+    if not aligned:
+        return 'direct'
+    if _wino2d(g, False, x2, infer):             # 3x3: the 2-D form; 1x3 / 3x1: the 1-D ones
+        return 'wino2d'
+    return 'wino' if _wino(g, False, x2, infer) else 'direct'
+
+
+def _dgrad_route(g, x2):
+    """kernel family of the input-gradient pass (of a convolution whose input takes a gradient)"""
+    if _wino2d(g, True, x2):
+        return 'wino2d'
+    w = _wino(g, True, x2)
+    if not w:
+        return 'direct'
+    if _wino43(g):
+        return 'wino43'
+    return 'wino_s2' if w == 2 else 'wino'       # (stride 2: the polyphase form, an operand of its own)
+
+
+# kind -> the `dgrad` argument of its pack (1-D: 0 forward | 1 input gradient | 2 stride-2 input gradient, the polyphase operand)
+_WINO_PACK_ARG = {'wino_fwd': 0, 'wino_dgrad': 1, 'wino_dgrad_s2': 2}
+_WINO2D_PACK_ARG = {'wino2d_fwd': 0, 'wino2d_dgrad': 1}
+
+
+def _pack_operands(weight, g, kinds, scale=None):
+    """The per-convolution packs of a weight, {kind: tensor}: one launch per kind, and the two direct layouts, where both are
+    asked for, out of ONE dynmm_pack_weight.  scale (inference): the folded BatchNorm factor per output channel rides in the filter
+    transforms (the direct kernel takes it as an argument instead: the direct layouts are the plain weight's)."""
+    lib, st, dims = _lib(), _stream(), (g.Co, g.Ci, g.KH, g.KW)
+    out = {}
+
+    def new(kind, n):
+        out[kind] = torch.empty(n, device=weight.device, dtype=torch.float32)
+        return out[kind].data_ptr()
+    if 'fwd' in kinds or 'dgrad' in kinds:
+        wp = new('fwd', lib.dynmm_packed_weight_floats(*dims, 0)) if 'fwd' in kinds else None
+        wpd = new('dgrad', lib.dynmm_packed_weight_floats(*dims, 1)) if 'dgrad' in kinds else None
+        L.check(lib.dynmm_pack_weight(_p(weight), wp, wpd, *dims, st), 'pack_weight')
+    for kind in kinds:
+        if kind in _WINO_PACK_ARG:
+            L.check(lib.dynmm_wino_pack(_p(weight), new(kind, lib.dynmm_wino_packed_floats(*dims)), _p(scale), *dims,
+                                        _WINO_PACK_ARG[kind], st), 'wino_pack')
+        elif kind == 'wino43_dgrad':
+            L.check(lib.dynmm_wino43_pack(_p(weight), new(kind, lib.dynmm_wino43_packed_floats(*dims)), *dims, st), 'wino43_pack')
+        elif kind in _WINO2D_PACK_ARG:
+            L.check(lib.dynmm_wino2d_pack(_p(weight), new(kind, lib.dynmm_wino2d_packed_floats(g.Co, g.Ci)), _p(scale), g.Co, g.Ci,
+                                          _WINO2D_PACK_ARG[kind], st), 'wino2d_pack')
+    return out
 
 
 WGRAD_STREAMS = 2        # weight-gradient side streams.  With the null stream and the depth-encoder stream that makes the FOUR busy
@@ -588,7 +648,7 @@ def _tile(co, m=1 << 30):
 
 
 
-def _timed(kind, g, call, nprob=1, extra=0, wino=False):
+def _timed(kind, g, call, nprob=1, extra=0, route='direct'):
     if PROFILE is None:
         return call()
     co = g.Ci if kind == 'dgrad' else g.Co
@@ -614,10 +674,10 @@ def _timed(kind, g, call, nprob=1, extra=0, wino=False):
             name = 'conv_co8_wgrad<direct,valu>'            # conv_small.hip: the gate conv's weight + bias gradient
     if kind != 'wgrad' and not generic and _lib().dynmm_conv2d_uses_operand_ring(C.byref(g), int(kind == 'dgrad')):
         name = f'conv_igemm_v5_{kind}<{"128x64" if co % 128 == 0 else "64x128"},kw{g.KW}>'      # conv_igemm_v5.hip
-    if wino == 22:                               # conv_wino2d.hip
+    if route == 'wino2d':                        # conv_wino2d.hip
         name = f'conv_wino2d_{kind}<co{128 if co % 128 == 0 else 64},3x3>'
-    elif wino:                                   # conv_wino.hip: one template instance per tile height, tap axis and direction
-        name = f'conv_wino{"43" if wino == 43 else ""}_{kind}<co{128 if co % 128 == 0 else 64},{g.KH}x{g.KW}{"s2" if g.SH * g.SW > 1 else ""}>'
+    elif route != 'direct':                      # conv_wino.hip: one template instance per tile height, tap axis and direction
+        name = f'conv_wino{"43" if route == "wino43" else ""}_{kind}<co{128 if co % 128 == 0 else 64},{g.KH}x{g.KW}{"s2" if g.SH * g.SW > 1 else ""}>'
     if kind == 'fwd':                            # conv_small.hip: *_eligible (the library's own dispatch rules)
         k5, k7 = (g.KH, g.KW, g.SH, g.SW, g.PH, g.PW) == (5, 5, 2, 2, 0, 0), (g.KH, g.KW, g.SH, g.SW, g.PH, g.PW) == (7, 7, 2, 2, 3, 3)
         if k5 and 5 <= g.Co <= 8 and g.Ci % 4 == 0 and g.Ci >= 16 and (g.c_split == g.Ci or g.c_split % (g.Ci // 4) == 0):
@@ -706,109 +766,95 @@ BN_BWD_FUSE = True       # (module attribute: tests switch it to compare with th
 BN_RELU_BITS = True
 
 
+# one registered weight of a PackedWeights; kinds: the set of operand kinds its passes read
+_PackedEntry = collections.namedtuple('_PackedEntry', 'weight Co Ci KH KW kinds')
+
+
 class PackedWeights:
     """The operand layouts of every conv weight a training step uses — the implicit-GEMM layouts (dynmm_pack_weight) and the
     Winograd filter transforms (dynmm_wino_pack) — produced by ONE launch each per step instead of one per convolution (186
     for config P).  A training step hands an instance to ops.step_scope(prepack=...): the first step runs the ordinary per-conv packs
-    and registers (weight, shape, which of the four operands its passes read); from then on pack() fills a static arena at
+    and registers (weight, shape, the operand kinds its passes read); from then on pack() fills a static arena at
     the start of the step body and the convolutions look their operands up.  Entries are valid between pack() and
     invalidate() only (the optimizer rewrites the weights after the body)."""
 
     def __init__(self):
-        self.reg = {}            # id(weight) -> [weight, Co, Ci, KH, KW, need_fwd, need_dgrad, wino_fwd, wino_dgrad, wino43_dgrad, wino2d_fwd, wino2d_dgrad]
-        self.slots = {}          # id(weight) -> (wp, wpd, utf, utd, utd43, ut2f, ut2d), None where not needed
-        self.arena = self.desc = self.wdesc = self.w43desc = self.w2desc = None
-        self.blocks = self.wblocks = self.nwino = self.w43blocks = self.nw43 = self.w2blocks = self.nw2 = 0
+        self.reg = {}            # id(weight) -> _PackedEntry: the weight, its shape and the operand kinds its passes read
+        self.slots = {}          # id(weight) -> {kind: view of the arena}
+        self.arena = None
+        self.launches = []       # one per operand family in use: (name, descriptor rows on the device, their count, thread blocks)
         self.valid = False
         self.dirty = False       # registrations since the arena was laid out
 
-    def register(self, weight, g, need_fwd=True, need_dgrad=False, wino_fwd=False, wino_dgrad=False, wino43_dgrad=False,
-                 wino2d_fwd=False, wino2d_dgrad=False):
+    def register(self, weight, g, kinds):
+        """a convolution of this step reads the operands `kinds` of `weight` (the entry holds the union over its convolutions)"""
         if not isinstance(weight, torch.nn.Parameter):
             return
-        flags = [bool(need_fwd), bool(need_dgrad), bool(wino_fwd), int(wino_dgrad), bool(wino43_dgrad),     # wino_dgrad: 0 | 1 | 2
-                 bool(wino2d_fwd), bool(wino2d_dgrad)]
         e = self.reg.get(id(weight))
         if e is None:
-            self.reg[id(weight)] = [weight, g.Co, g.Ci, g.KH, g.KW] + flags
+            e = self.reg[id(weight)] = _PackedEntry(weight, g.Co, g.Ci, g.KH, g.KW, set())
+        if not e.kinds.issuperset(kinds):
+            e.kinds.update(kinds)
             self.dirty = True
-        else:
-            for i, f in enumerate(flags):
-                if f and e[5 + i] != f:
-                    # (wino_dgrad is tri-state — 1: stride-1 transform, 2: stride-2 polyphase operand; the two are different
-                    # operands of different kernels, so a weight is registered with exactly one of them: store the value)
-                    if i == 3 and e[5 + i] and f:
-                        raise L.DynmmHipError('a convolution weight was registered with both Winograd input-gradient operand kinds')
-                    e[5 + i] = f
-                    self.dirty = True
 
-    def lookup(self, weight, need_fwd=True, need_dgrad=False, wino_fwd=False, wino_dgrad=False, wino43_dgrad=False,
-               wino2d_fwd=False, wino2d_dgrad=False):
-        if not self.valid:
-            return None
-        s = self.slots.get(id(weight))
-        if s is None:
-            return None
-        for need, t in zip((need_fwd, need_dgrad, wino_fwd, wino_dgrad, wino43_dgrad, wino2d_fwd, wino2d_dgrad), s):
-            if need and t is None:
-                return None
-        if wino_dgrad and self.reg[id(weight)][5 + 3] != int(wino_dgrad):
-            return None                          # the slot holds the other operand kind (stride-1 transform vs stride-2 polyphase)
-        return s
+    def lookup(self, weight, kinds):
+        """{kind: tensor} holding every one of `kinds`, or None (not packed, or one of them not registered)"""
+        ops = self.slots.get(id(weight)) if self.valid else None
+        if ops is not None:
+            for kind in kinds:
+                if kind not in ops:
+                    return None
+        return ops
 
     def _layout(self):
         lib = _lib()
         ents = list(self.reg.values())
-        dev = ents[0][0].device
-        base = min(e[0].data_ptr() for e in ents)
+        dev = ents[0].weight.device
+        base = min(e.weight.data_ptr() for e in ents)
         off, blk, wblk, w43blk, w2blk, rows, wrows, w43rows, w2rows = 0, 0, 0, 0, 0, [], [], [], []
         spans = {}
-        for w, Co, Ci, KH, KW, nf_, nd, wf, wd, wd43, w2f, w2d in ents:
+        for w, Co, Ci, KH, KW, kinds in ents:
             src = (w.data_ptr() - base) // 4
-            span = [None] * 7
-            # the multi-tensor pack always writes the forward layout; the input-gradient layout only where a direct
-            # kernel reads it (dynmm_pack_weight_multi's descriptor: dst_dgrad = -1 otherwise)
-            nf = lib.dynmm_packed_weight_floats(Co, Ci, KH, KW, 0)
-            ndg = lib.dynmm_packed_weight_floats(Co, Ci, KH, KW, 1) if nd else 0
-            if nf_ or nd:
-                dstf = off
-                off += (nf + 3) & ~3             # rows stay 16-byte aligned (the kernels' dwordx4 path)
-                dstd = off if nd else -1
-                off += (ndg + 3) & ~3
+            span = spans[id(w)] = {}             # kind -> (offset, floats)
+            if 'fwd' in kinds or 'dgrad' in kinds:
+                # the multi-tensor pack always writes the forward layout; the input-gradient layout only where a direct
+                # kernel reads it (dynmm_pack_weight_multi's descriptor: dst_dgrad = -1 otherwise)
+                nd = 'dgrad' in kinds
+                nf = lib.dynmm_packed_weight_floats(Co, Ci, KH, KW, 0)
+                ndg = lib.dynmm_packed_weight_floats(Co, Ci, KH, KW, 1) if nd else 0
+                dstf, dstd = off, (off + _up4(nf) if nd else -1)
+                off += _up4(nf) + _up4(ndg)      # rows stay 16-byte aligned (the kernels' dwordx4 path)
                 rows.append([src, dstf, dstd, Co | (Ci << 32), (KH * KW) | (blk << 32)])
-                span[0] = (dstf, nf)
-                span[1] = (dstd, ndg) if nd else None
+                span['fwd'] = (dstf, nf)
+                if nd:
+                    span['dgrad'] = (dstd, ndg)
                 blk += lib.dynmm_pack_weight_multi_blocks(Co, Ci, KH, KW, int(nd))
-            nu = lib.dynmm_wino_packed_floats(Co, Ci, KH, KW)
-            for slot, dgrad, on in ((2, 0, wf), (3, 2 if wd == 2 else 1, wd)):     # (wd == 2: stride-2 polyphase operand)
-                if on:
+            for kind, dgrad in _WINO_PACK_ARG.items():
+                if kind in kinds:
+                    nu = lib.dynmm_wino_packed_floats(Co, Ci, KH, KW)
                     wrows.append([src, off, Co | (Ci << 32), KH | (KW << 8) | (dgrad << 16) | (wblk << 32)])
-                    span[slot] = (off, nu)
+                    span[kind] = (off, nu)
                     off += nu                    # a multiple of 4 floats
                     wblk += lib.dynmm_wino_pack_multi_blocks(Co, Ci, KH, KW)
-            if wd43:
+            if 'wino43_dgrad' in kinds:
                 nu43 = lib.dynmm_wino43_packed_floats(Co, Ci, KH, KW)
                 w43rows.append([src, off, Co | (Ci << 32), KH | (KW << 8) | (w43blk << 32)])
-                span[4] = (off, nu43)
-                off += (nu43 + 3) & ~3
+                span['wino43_dgrad'] = (off, nu43)
+                off += _up4(nu43)
                 w43blk += lib.dynmm_wino43_pack_multi_blocks(Co, Ci, KH, KW)
-            nu2 = lib.dynmm_wino2d_packed_floats(Co, Ci) if (w2f or w2d) else 0
-            for slot, dgrad, on in ((5, 0, w2f), (6, 1, w2d)):
-                if on:
+            for kind, dgrad in _WINO2D_PACK_ARG.items():
+                if kind in kinds:
+                    nu2 = lib.dynmm_wino2d_packed_floats(Co, Ci)
                     w2rows.append([src, off, Co | (Ci << 32), (dgrad << 16) | (w2blk << 32)])
-                    span[slot] = (off, nu2)
+                    span[kind] = (off, nu2)
                     off += nu2                   # a multiple of 4 floats
                     w2blk += lib.dynmm_wino2d_pack_multi_blocks(Co, Ci, dgrad)
-            spans[id(w)] = span
         self.arena = torch.empty(off, device=dev, dtype=torch.float32)
-        self.desc = torch.tensor(rows, dtype=torch.int64).to(dev) if rows else None
-        self.wdesc = torch.tensor(wrows, dtype=torch.int64).to(dev) if wrows else None
-        self.w43desc = torch.tensor(w43rows, dtype=torch.int64).to(dev) if w43rows else None
-        self.w2desc = torch.tensor(w2rows, dtype=torch.int64).to(dev) if w2rows else None
-        self.ndesc, self.nwino, self.nw43, self.nw2 = len(rows), len(wrows), len(w43rows), len(w2rows)
-        self.base, self.blocks, self.wblocks, self.w43blocks, self.w2blocks = base, blk, wblk, w43blk, w2blk
-        self.slots = {k: tuple(self.arena[sp[0]:sp[0] + sp[1]] if sp is not None else None for sp in span)
-                      for k, span in spans.items()}
+        self.base = base
+        self.launches = [(name, torch.tensor(r, dtype=torch.int64).to(dev), len(r), b) for name, r, b in
+                         (('pack_weight_multi', rows, blk), ('wino_pack_multi', wrows, wblk), ('wino43_pack_multi', w43rows, w43blk),
+                          ('wino2d_pack_multi', w2rows, w2blk)) if r]
+        self.slots = {k: {kind: self.arena[o:o + n] for kind, (o, n) in span.items()} for k, span in spans.items()}
         self.dirty = False
 
     def pack(self):
@@ -820,18 +866,8 @@ class PackedWeights:
             if torch.cuda.is_current_stream_capturing():
                 return                           # layout changes allocate: not inside a capture
             self._layout()
-        if self.desc is not None:
-            L.check(_lib().dynmm_pack_weight_multi(C.c_void_p(self.base), _p(self.arena), self.desc.data_ptr(), self.ndesc,
-                                                   self.blocks, _stream()), 'pack_weight_multi')
-        if self.wdesc is not None:
-            L.check(_lib().dynmm_wino_pack_multi(C.c_void_p(self.base), _p(self.arena), self.wdesc.data_ptr(), self.nwino,
-                                                 self.wblocks, _stream()), 'wino_pack_multi')
-        if self.w43desc is not None:
-            L.check(_lib().dynmm_wino43_pack_multi(C.c_void_p(self.base), _p(self.arena), self.w43desc.data_ptr(), self.nw43,
-                                                   self.w43blocks, _stream()), 'wino43_pack_multi')
-        if self.w2desc is not None:
-            L.check(_lib().dynmm_wino2d_pack_multi(C.c_void_p(self.base), _p(self.arena), self.w2desc.data_ptr(), self.nw2,
-                                                   self.w2blocks, _stream()), 'wino2d_pack_multi')
+        for name, desc, n, blocks in self.launches:
+            L.check(getattr(_lib(), 'dynmm_' + name)(C.c_void_p(self.base), _p(self.arena), desc.data_ptr(), n, blocks, _stream()), name)
         self.valid = True
 
     def invalidate(self):
@@ -904,95 +940,58 @@ class _Conv2d(Function):
         need_dx = ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1])
         y = torch.empty((g.N, g.Co, g.Ho, g.Wo), device=x.device, dtype=torch.float32)
         # (the Winograd kernels read their input with 16-byte loads; an input off that grid takes the direct kernels)
-        w2f = _wino2d(g, False, x2) and x.data_ptr() % 16 == 0          # 3x3: the 2-D form; 1x3 / 3x1: the 1-D ones
-        w2d = need_dx and _wino2d(g, True, x2)
-        wino_f = not w2f and _wino(g, False, x2) and x.data_ptr() % 16 == 0
-        wino_d = need_dx and not w2d and _wino(g, True, x2)
-        wino_d43 = wino_d and _wino43(g)
-        wino_d = 0 if wino_d43 else int(wino_d or 0)          # 0 | 1 (stride 1) | 2 (stride 2: polyphase form)
-        need_wp, need_wpd = not (wino_f or w2f), need_dx and not (wino_d or wino_d43 or w2d)
+        fwd = _fwd_route(g, x2, x.data_ptr() % 16 == 0)
+        dgrad = _dgrad_route(g, x2) if need_dx else None
+        kinds = (_FWD_KIND[fwd], _DGRAD_KIND[dgrad]) if need_dx else (_FWD_KIND[fwd],)
         # (a Linear / Conv1d weight arrives as a [Co, Ci, 1, 1] alias of its parameter: same memory, so the parameter keys the pack)
         wkey = w_owner if w_owner is not None else weight
-        wp = wpd = utf = utd = utd43 = ut2f = ut2d = None
         prepack = _STEP.prepack if _STEP is not None else None
-        pre = prepack.lookup(wkey, need_wp, need_wpd, wino_f, wino_d, wino_d43, w2f, w2d) if prepack is not None else None
-        if pre is not None:
-            wp, wpd, utf, utd, utd43, ut2f, ut2d = pre           # packed by the step's multi-tensor launches
-        else:
-            if need_wp or need_wpd:
-                wp = torch.empty(lib.dynmm_packed_weight_floats(g.Co, g.Ci, g.KH, g.KW, 0), device=x.device,
-                                 dtype=torch.float32) if need_wp else None
-                wpd = torch.empty(lib.dynmm_packed_weight_floats(g.Co, g.Ci, g.KH, g.KW, 1), device=x.device,
-                                  dtype=torch.float32) if need_wpd else None
-                L.check(lib.dynmm_pack_weight(_p(weight), _p(wp), _p(wpd), g.Co, g.Ci, g.KH, g.KW, st), 'pack_weight')
-            nu = lib.dynmm_wino_packed_floats(g.Co, g.Ci, g.KH, g.KW) if (wino_f or wino_d) else 0
-            if wino_f:
-                utf = torch.empty(nu, device=x.device, dtype=torch.float32)
-                L.check(lib.dynmm_wino_pack(_p(weight), _p(utf), None, g.Co, g.Ci, g.KH, g.KW, 0, st), 'wino_pack')
-            if wino_d:
-                utd = torch.empty(nu, device=x.device, dtype=torch.float32)
-                L.check(lib.dynmm_wino_pack(_p(weight), _p(utd), None, g.Co, g.Ci, g.KH, g.KW, int(wino_d), st), 'wino_pack')
-            if wino_d43:
-                utd43 = torch.empty(lib.dynmm_wino43_packed_floats(g.Co, g.Ci, g.KH, g.KW), device=x.device, dtype=torch.float32)
-                L.check(lib.dynmm_wino43_pack(_p(weight), _p(utd43), g.Co, g.Ci, g.KH, g.KW, st), 'wino43_pack')
-            if w2f or w2d:
-                nu2 = lib.dynmm_wino2d_packed_floats(g.Co, g.Ci)
-                if w2f:
-                    ut2f = torch.empty(nu2, device=x.device, dtype=torch.float32)
-                    L.check(lib.dynmm_wino2d_pack(_p(weight), _p(ut2f), None, g.Co, g.Ci, 0, st), 'wino2d_pack')
-                if w2d:
-                    ut2d = torch.empty(nu2, device=x.device, dtype=torch.float32)
-                    L.check(lib.dynmm_wino2d_pack(_p(weight), _p(ut2d), None, g.Co, g.Ci, 1, st), 'wino2d_pack')
+        packed = prepack.lookup(wkey, kinds) if prepack is not None else None        # packed by the step's multi-tensor launches
+        if packed is None:
+            packed = _pack_operands(weight, g, kinds)
             if prepack is not None:
-                prepack.register(wkey, g, need_wp, need_wpd, wino_f, wino_d, wino_d43, w2f, w2d)
-        if w2f:
+                prepack.register(wkey, g, kinds)
+        wf = packed[kinds[0]]
+        if fwd == 'wino2d':
             sums, ns = None, 0
             if stats is not None and act == L.ACT_NONE and g.Co % 64 == 0:
                 # the consumer is a training-mode BatchNorm: its batch statistics come out of this launch
                 ns = lib.dynmm_conv2d_wino2d_stats_slots(C.byref(g))
-                sums, zeroed = _zero_sums(2 * g.Co * ns, x.device)
-                if not zeroed:
-                    sums.zero_()
-                stats['sums'] = sums
-            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_wino2d_fwd(_p(x), _p(ut2f), _p(bias), None, _p(y), _p(sums), ns,
-                                                                         C.byref(g), act, st), wino=22), 'conv2d_wino2d_fwd')
-        elif (wino_f and stats is not None and act == L.ACT_NONE and g.KW == 3 and
+                stats['sums'] = sums = _zeroed_sums(2 * g.Co * ns, x.device)
+            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_wino2d_fwd(_p(x), _p(wf), _p(bias), None, _p(y), _p(sums), ns,
+                                                                         C.byref(g), act, st), route=fwd), 'conv2d_wino2d_fwd')
+        elif (fwd == 'wino' and stats is not None and act == L.ACT_NONE and g.KW == 3 and
                 lib.dynmm_conv2d_wino_fwd_stats_supported(C.byref(g))):
             # the consumer is a training-mode BatchNorm: its batch statistics come out of this launch (stats: a holder the
             # conv2d() wrapper hangs on the output tensor for batch_norm_act to find)
             ns = lib.dynmm_conv2d_wino_fwd_stats_slots(C.byref(g))
-            sums, zeroed = _zero_sums(2 * g.Co * ns, x.device)
-            if not zeroed:
-                sums.zero_()
-            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_wino_fwd_stats(_p(x), _p(utf), _p(bias), _p(y), _p(sums), ns,
-                                                                             C.byref(g), st), wino=True), 'conv2d_wino_fwd_stats')
+            sums = _zeroed_sums(2 * g.Co * ns, x.device)
+            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_wino_fwd_stats(_p(x), _p(wf), _p(bias), _p(y), _p(sums), ns,
+                                                                             C.byref(g), st), route=fwd), 'conv2d_wino_fwd_stats')
             stats['sums'] = sums
-        elif wino_f:
-            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_wino_fwd(_p(x), _p(utf), _p(bias), None, _p(y), C.byref(g), act, st),
-                           wino=True), 'conv2d_wino_fwd')
+        elif fwd == 'wino':
+            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_wino_fwd(_p(x), _p(wf), _p(bias), None, _p(y), C.byref(g), act, st),
+                           route=fwd), 'conv2d_wino_fwd')
         elif (stats is not None and act == L.ACT_NONE and x2 is None and
                 lib.dynmm_conv2d_stem_fwd_stats_supported(C.byref(g))):
             # a ResNet stem feeding its training-mode BatchNorm: the batch statistics come out of the convolution's epilogue
-            sums, zeroed = _zero_sums(2 * g.Co, x.device)
-            if not zeroed:
-                sums.zero_()
-            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_stem_fwd_stats(_p(x), _p(wp), _p(bias), _p(y), _p(sums),
+            sums = _zeroed_sums(2 * g.Co, x.device)
+            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_stem_fwd_stats(_p(x), _p(wf), _p(bias), _p(y), _p(sums),
                                                                              C.byref(g), st)), 'conv2d_stem_fwd_stats')
             stats['sums'] = sums
         else:
-            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_fwd(_p(x), _p(x2), _p(wp), None, _p(bias), None, _p(y),
+            L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_fwd(_p(x), _p(x2), _p(wf), None, _p(bias), None, _p(y),
                                                                   C.byref(g), act, st)), 'conv2d_fwd')
         ctx.geom = g
         ctx.act = act
         ctx.has_bias = bias is not None
         ctx.has_x2 = x2 is not None
-        ctx.wino_d = 22 if w2d else (43 if wino_d43 else (23 if wino_d else 0))
+        ctx.dgrad_route = dgrad           # kernel family of the input-gradient pass (None: the input takes no gradient)
         ctx.mask_input = mask_input       # x is a ReLU output: apply [x > 0] in the dgrad epilogue
         ctx.defer_mask = defer_mask       # our own ReLU backward is applied by the consumer's dgrad
         ctx.link = link
         ctx.bn_link = bn_link
-        ctx.save_for_backward(x, x2, ut2d if w2d else (utd43 if wino_d43 else (utd if wino_d else wpd)),
-                              y if (act != L.ACT_NONE and not defer_mask) else None)
+        ctx.save_for_backward(x, x2, packed[kinds[1]] if need_dx else None, y if (act != L.ACT_NONE and not defer_mask) else None)
         ctx.wshape = tuple(weight.shape)
         # w_owner: the nn.Parameter that `weight` is a reshaped view of (Linear / Conv1d weights used as 1x1 convs): its
         # `.grad` has the same memory layout, so the in-place gradient protocol can write straight into it
@@ -1036,7 +1035,8 @@ class _Conv2d(Function):
             if ctx.link is not None and ctx.link.dres is not None:
                 accum, ctx.link.dres = ctx.link.dres, None
             extra = (mask is not None) + (accum is not None)
-            if ctx.wino_d:
+            route = ctx.dgrad_route
+            if route != 'direct':
                 # 16-byte loads of gy, 8-byte accesses to the epilogue operands: tensors off that grid (views handed in by the
                 # caller) are copied into fresh allocations first
                 gyw = gy if gy.data_ptr() % 16 == 0 else gy.clone()
@@ -1045,36 +1045,32 @@ class _Conv2d(Function):
                 # ((ctx.link is None) == (accum is None): when this block has an identity branch its gradient must have ARRIVED here
                 #  through the link — had it taken the autograd route instead (link.dres never set), the launch below would mask
                 #  the convolution's part only while telling the BatchNorm backward the sum is masked: ADVICE r5)
-                if (bl is not None and bl.x is not None and bl.bits is not None and ctx.wino_d == 23 and mask is None and
+                if (bl is not None and bl.x is not None and bl.bits is not None and route in _WINO_F23 and mask is None and
                         (ctx.link is None) == (accum is None) and
                         bl.x.data_ptr() % 8 == 0 and (g.H * g.W) % 4 == 0 and
                         lib.dynmm_conv2d_wino_dgrad_bnred_supported(C.byref(g))):
                     # x = relu(BN(c) + identity), this convolution and the identity branch behind `accum` its only consumers: the
                     # complete gradient of that output is formed here — mask it with the forward's decisions and leave the
                     # BatchNorm's backward reductions with the link
-                    sums, zeroed = _zero_sums(2 * g.Ci * lib.dynmm_conv2d_wino_dgrad_bnred_slots(C.byref(g)), dx.device)
-                    if not zeroed:
-                        sums.zero_()
+                    sums = _zeroed_sums(2 * g.Ci * lib.dynmm_conv2d_wino_dgrad_bnred_slots(C.byref(g)), dx.device)
                     L.check(_timed('dgrad', g, lambda: lib.dynmm_conv2d_wino_dgrad_bnred2(
                         _p(gyw), _p(wpd), _p(accum), _p(bl.x), _p(bl.bits), _p(bl.mean), _p(bl.invstd), _p(sums), _p(dx),
-                        C.byref(g), st), extra=2, wino=ctx.wino_d), 'conv2d_wino_dgrad_bnred2')
+                        C.byref(g), st), extra=2, route=route), 'conv2d_wino_dgrad_bnred2')
                     bl.sums, bl.premasked = sums, True
-                elif (bl is not None and bl.x is not None and bl.bits is None and ctx.wino_d == 23 and mask is None and
+                elif (bl is not None and bl.x is not None and bl.bits is None and route in _WINO_F23 and mask is None and
                         accum is None and
                         bl.x.data_ptr() % 8 == 0 and lib.dynmm_conv2d_wino_dgrad_bnred_supported(C.byref(g))):
                     # x = relu(BN(c)) of a training-mode BatchNorm: mask by [BN(c) > 0] here and leave that BatchNorm's backward
                     # reductions with the link (its backward, which runs next, skips its reduction pass)
-                    sums, zeroed = _zero_sums(2 * g.Ci * lib.dynmm_conv2d_wino_dgrad_bnred_slots(C.byref(g)), dx.device)
-                    if not zeroed:
-                        sums.zero_()
+                    sums = _zeroed_sums(2 * g.Ci * lib.dynmm_conv2d_wino_dgrad_bnred_slots(C.byref(g)), dx.device)
                     L.check(_timed('dgrad', g, lambda: lib.dynmm_conv2d_wino_dgrad_bnred(
                         _p(gyw), _p(wpd), _p(bl.x), _p(bl.mean), _p(bl.invstd), _p(bl.gamma), _p(bl.beta), _p(sums), _p(dx),
-                        C.byref(g), st), extra=1, wino=ctx.wino_d), 'conv2d_wino_dgrad_bnred')
+                        C.byref(g), st), extra=1, route=route), 'conv2d_wino_dgrad_bnred')
                     bl.sums = sums
                 else:
-                    fn = {22: lib.dynmm_conv2d_wino2d_dgrad, 43: lib.dynmm_conv2d_wino43_dgrad}.get(ctx.wino_d, lib.dynmm_conv2d_wino_dgrad)
+                    fn = {'wino2d': lib.dynmm_conv2d_wino2d_dgrad, 'wino43': lib.dynmm_conv2d_wino43_dgrad}.get(route, lib.dynmm_conv2d_wino_dgrad)
                     L.check(_timed('dgrad', g, lambda: fn(_p(gyw), _p(wpd), _p(mask), _p(accum), _p(dx), C.byref(g), st),
-                                   extra=extra, wino=ctx.wino_d), 'conv2d_wino_dgrad')
+                                   extra=extra, route=route), 'conv2d_wino_dgrad')
             else:
                 L.check(_timed('dgrad', g, lambda: lib.dynmm_conv2d_dgrad(_p(gy), _p(wpd), _p(mask), _p(accum), _p(dx),
                                                                           _p(dx2), C.byref(g), st), extra=extra), 'conv2d_dgrad')
@@ -1186,6 +1182,7 @@ def note_mutation():
 # weights).  engine.InferStep keys its graphs on the version stamp of every parameter and buffer and drops them when it moves,
 # so its captures may read the cached operands instead (True only inside InferStep._capture): ~200 launches less per replay.
 CAPTURE_EVAL_CACHE = False
+_EVAL_CACHE = {'direct': '_dynmm_eval_cache', 'wino': '_dynmm_eval_cache_wino', 'wino2d': '_dynmm_eval_cache_wino2d'}      # route -> attribute
 
 
 def conv2d_fused_eval(x, weight, conv_bias, bn, act=None, residual=None, stride=1, padding=0, x2=None):
@@ -1202,10 +1199,8 @@ def conv2d_fused_eval(x, weight, conv_bias, bn, act=None, residual=None, stride=
     # address + in-place version counter of every tensor they derive from (load_state_dict / optimizer steps bump
     # the versions) and the mutation generation above: a steady-state forward launches only the conv.
     srcs = [weight, conv_bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-    ok_ptrs = x.data_ptr() % 16 == 0 and (residual is None or residual.data_ptr() % 8 == 0)
-    wino2 = _wino2d(g, False, x2, infer=True) and ok_ptrs
-    wino = not wino2 and _wino(g, False, x2, infer=True) and ok_ptrs
-    slot = '_dynmm_eval_cache_wino2d' if wino2 else ('_dynmm_eval_cache_wino' if wino else '_dynmm_eval_cache')
+    route = _fwd_route(g, x2, x.data_ptr() % 16 == 0 and (residual is None or residual.data_ptr() % 8 == 0), infer=True)
+    slot = _EVAL_CACHE[route]
     stamp = (_MUTATION_GEN[0],) + tuple((t.data_ptr(), t._version) for t in srcs if t is not None) + \
         ((float(bn.eps),) if bn is not None else ())
     hit = getattr(weight, slot, None)
@@ -1220,28 +1215,21 @@ def conv2d_fused_eval(x, weight, conv_bias, bn, act=None, residual=None, stride=
                                       _p(conv_bias), _p(scale), _p(shift), g.Co, bn.eps, st), 'bn_fold')
         else:
             shift = _chk(conv_bias, 'bias')
-        if wino2:
-            wp = torch.empty(lib.dynmm_wino2d_packed_floats(g.Co, g.Ci), device=dev, dtype=torch.float32)
-            L.check(lib.dynmm_wino2d_pack(_p(weight), _p(wp), _p(scale), g.Co, g.Ci, 0, st), 'wino2d_pack')
+        # (filter transforms of scale[co] * w: the folded BatchNorm factor rides in the operand, the kernel adds the shift)
+        kind = _FWD_KIND[route]
+        wp = _pack_operands(weight, g, (kind,), scale)[kind]
+        if route != 'direct':
             scale = None
-        elif wino:
-            # filter transforms of scale[co] * w: the folded BatchNorm factor rides in the operand, the kernel adds the shift
-            wp = torch.empty(lib.dynmm_wino_packed_floats(g.Co, g.Ci, g.KH, g.KW), device=dev, dtype=torch.float32)
-            L.check(lib.dynmm_wino_pack(_p(weight), _p(wp), _p(scale), g.Co, g.Ci, g.KH, g.KW, 0, st), 'wino_pack')
-            scale = None
-        else:
-            wp = torch.empty(lib.dynmm_packed_weight_floats(g.Co, g.Ci, g.KH, g.KW, 0), device=dev, dtype=torch.float32)
-            L.check(lib.dynmm_pack_weight(_p(weight), _p(wp), None, g.Co, g.Ci, g.KH, g.KW, st), 'pack_weight')
         if not torch.cuda.is_current_stream_capturing():
             setattr(weight, slot, (stamp, (wp, scale, shift)))
     y = torch.empty((g.N, g.Co, g.Ho, g.Wo), device=dev, dtype=torch.float32)
-    if wino2:
+    if route == 'wino2d':
         L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_wino2d_fwd(_p(x), _p(wp), _p(shift), _p(residual), _p(y), None, 0, C.byref(g),
-                                                                     ACT[act], st), extra=int(residual is not None), wino=22),
+                                                                     ACT[act], st), extra=int(residual is not None), route=route),
                 'conv2d_wino2d_fwd')
-    elif wino:
+    elif route == 'wino':
         L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_wino_fwd(_p(x), _p(wp), _p(shift), _p(residual), _p(y), C.byref(g),
-                                                                   ACT[act], st), extra=int(residual is not None), wino=True),
+                                                                   ACT[act], st), extra=int(residual is not None), route=route),
                 'conv2d_wino_fwd')
     else:
         L.check(_timed('fwd', g, lambda: lib.dynmm_conv2d_fwd(_p(x), _p(x2), _p(wp), _p(scale), _p(shift), _p(residual),
@@ -1282,6 +1270,14 @@ def _zero_sums(n, device):
     t = a['buf'][a['off']:a['off'] + n]
     a['off'] += n
     return t, 1
+
+
+def _zeroed_sums(n, device):
+    """n zero doubles, for a kernel that only adds to them"""
+    sums, zeroed = _zero_sums(n, device)
+    if not zeroed:
+        sums.zero_()
+    return sums
 
 
 class _BatchNormAct(Function):

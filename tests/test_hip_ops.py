@@ -982,21 +982,27 @@ def test_winograd_operands_from_the_step_pack(ops):
     st = torch.cuda.current_stream().cuda_stream
     ws = [torch.nn.Parameter(rnd(*s, seed=i).cuda()) for i, s in enumerate([(128, 64, 1, 3), (64, 64, 3, 1), (128, 128, 3, 3)])]
     pw = ops.PackedWeights()
+
+    def kinds_of(w):
+        Co, Ci, KH, KW = w.shape
+        if KH * KW == 9:
+            return ('fwd', 'wino2d_fwd', 'wino2d_dgrad')
+        return ('fwd', 'wino_fwd', 'wino_dgrad') + (('wino43_dgrad',) if KW == 3 else ())
     for w in ws:
         Co, Ci, KH, KW = w.shape
-        g = L.ConvGeom(2, Ci, 16, 16, Co, 16, 16, KH, KW, 1, 1, KH // 2, KW // 2, Ci)
-        k33 = KH * KW == 9
-        pw.register(w, g, True, False, not k33, not k33, KW == 3 and not k33, k33, k33)
+        pw.register(w, L.ConvGeom(2, Ci, 16, 16, Co, 16, 16, KH, KW, 1, 1, KH // 2, KW // 2, Ci), kinds_of(w))
     pw.pack()
     torch.cuda.synchronize()
     for w in ws:
         Co, Ci, KH, KW = w.shape
         k33 = KH * KW == 9
         h13 = KW == 3 and not k33
-        wp, wpd, utf, utd, utd43, ut2f, ut2d = pw.lookup(w, True, False, not k33, not k33, h13, k33, k33)
-        assert wpd is None and pw.lookup(w, True, True) is None          # the direct input-gradient layout was not requested
-        assert (ut2f is not None) == k33 and (k33 or pw.lookup(w, True, False, True, True, h13, True) is None)
-        assert (utf is None) == k33 and (not k33 or pw.lookup(w, True, False, True) is None)
+        got = pw.lookup(w, kinds_of(w))
+        utf, utd, utd43, ut2f, ut2d = (got.get(k) for k in ('wino_fwd', 'wino_dgrad', 'wino43_dgrad', 'wino2d_fwd', 'wino2d_dgrad'))
+        assert got['fwd'] is not None and set(got) == set(kinds_of(w))
+        assert 'dgrad' not in got and pw.lookup(w, ('fwd', 'dgrad')) is None   # the direct input-gradient layout was not requested
+        assert (ut2f is not None) == k33 and (k33 or pw.lookup(w, kinds_of(w) + ('wino2d_fwd',)) is None)
+        assert (utf is None) == k33 and (not k33 or pw.lookup(w, ('fwd', 'wino_fwd')) is None)
         assert lib.dynmm_wino_packed_floats(Co, Ci, KH, KW) == (0 if k33 else 4 * max(Ci * ((Co + 63) // 64 * 64), Co * ((Ci + 63) // 64 * 64)))
         assert lib.dynmm_wino43_packed_floats(Co, Ci, KH, KW) == (6 * Co * Ci if h13 else 0)
         for dgrad, got in ((0, ut2f), (1, ut2d)) if k33 else ():         # the 2-D F(2x2,3x3) operands (csrc/conv_wino2d.hip)
@@ -1021,6 +1027,109 @@ def test_winograd_operands_from_the_step_pack(ops):
                 L.ConvGeom(2, 20, 16, 16, 60, 16, 16, 1, 3, 1, 1, 0, 1, 20),     # neither channel count fits a 64-row tile
                 L.ConvGeom(2, 64, 16, 16, 64, 16, 16, 1, 1, 1, 1, 0, 0, 64)):    # 1x1
         assert lib.dynmm_conv2d_wino_supported(C.byref(bad), 0) == 0 and lib.dynmm_conv2d_wino_supported(C.byref(bad), 1) == 0
+
+
+_FAMILY_NAMES = {('fwd', 'direct'): 'conv_igemm', ('fwd', 'wino'): 'conv_wino_fwd', ('fwd', 'wino2d'): 'conv_wino2d_fwd',
+                 ('dgrad', 'direct'): 'conv_igemm', ('dgrad', 'wino'): 'conv_wino_dgrad', ('dgrad', 'wino_s2'): 'conv_wino_dgrad',
+                 ('dgrad', 'wino43'): 'conv_wino43_dgrad', ('dgrad', 'wino2d'): 'conv_wino2d_dgrad'}
+
+
+@pytest.mark.parametrize('k,stride', [((1, 3), (1, 1)), ((3, 1), (1, 1)), ((3, 3), (1, 1)), ((3, 1), (2, 1)), ((1, 1), (1, 1))])
+def test_conv2d_route_and_launch_agree(ops, k, stride):
+    """ops._fwd_route / ops._dgrad_route name the kernel family of each pass under every WINO / WINO_DGRAD setting, and the
+    launches ops.conv2d(...).backward() records in ops.PROFILE are that family's (N = 2, C = 64, 16 x 16)."""
+    p = (k[0] // 2, k[1] // 2)
+    x, w, b = rnd(2, 64, 16, 16, seed=1), rnd(64, 64, *k, seed=2, scale=0.1), rnd(64, seed=3, scale=0.1)
+    old, old_d = ops.WINO, ops.WINO_DGRAD
+    try:
+        for wino in ('all', 'fwd', 'dgrad', '0'):
+            for wino_d in ('43h', '23'):
+                ops.WINO, ops.WINO_DGRAD = wino, wino_d
+                if k == (1, 1):
+                    fwd = dgrad = 'direct'
+                elif stride != (1, 1):                     # stride 2: only the input gradient has a Winograd (polyphase) form
+                    fwd, dgrad = 'direct', 'wino_s2'
+                elif k == (3, 3):
+                    fwd = dgrad = 'wino2d'
+                else:                                       # F(4,3) for the input gradients of the 1x3 filters under '43h'
+                    fwd, dgrad = 'wino', ('wino43' if (k == (1, 3) and wino_d == '43h') else 'wino')
+                fwd = fwd if wino in ('all', 'fwd') else 'direct'
+                dgrad = dgrad if wino in ('all', 'dgrad') else 'direct'
+                tag = (k, stride, wino, wino_d)
+                xg, wg, bg = [t.cuda().requires_grad_(True) for t in (x, w, b)]
+                g = ops._geom(xg, None, wg, stride, p)
+                assert ops._fwd_route(g, None, True) == fwd and ops._fwd_route(g, None, False) == 'direct', tag
+                assert ops._dgrad_route(g, None) == dgrad, tag
+                ops.PROFILE = calls = []
+                y = ops.conv2d(xg, wg, bg, stride, p)
+                y.backward(torch.ones_like(y))
+                ops.PROFILE = None
+                names = {kind: [c[0] for c in calls if c[5][0] == kind] for kind in ('fwd', 'dgrad')}
+                assert len(names['fwd']) == 1 and names['fwd'][0].startswith(_FAMILY_NAMES['fwd', fwd]), (tag, names)
+                assert len(names['dgrad']) == 1 and names['dgrad'][0].startswith(_FAMILY_NAMES['dgrad', dgrad]), (tag, names)
+                assert names['dgrad'][0].endswith('s2>') == (dgrad == 'wino_s2'), (tag, names)
+    finally:
+        ops.WINO, ops.WINO_DGRAD, ops.PROFILE = old, old_d, None
+    torch.cuda.synchronize()
+
+
+def test_one_weight_on_two_forward_families_under_a_prepack(ops):
+    """One 1x3 weight read by a convolution of an aligned input (Winograd forward) and by one of an input 4 bytes off the 16-byte
+    grid (direct forward), inside ops.step_scope(prepack=...): its entry holds both forward operands, the second step packs nothing
+    per convolution, and outputs and gradients equal those of the same calls without a prepack bit for bit."""
+    lib = ops._lib()
+    shape = (2, 64, 16, 16)
+    n = 2 * 64 * 16 * 16
+    flat = torch.zeros(n + 4, device='cuda')
+    flat[1:1 + n] = rnd(n, seed=2).cuda()
+    xs = [rnd(*shape, seed=1).cuda(), flat[1:1 + n].view(shape)]
+    assert [t.data_ptr() % 16 for t in xs] == [0, 4]
+    gys = [rnd(*shape, seed=3).cuda(), rnd(*shape, seed=4).cuda()]
+    w0 = rnd(64, 64, 1, 3, seed=5, scale=0.1)
+
+    def run(pw):
+        w = torch.nn.Parameter(w0.clone().cuda())
+        out, packs = [], []
+        for step in range(2):
+            with _CallSpy(lib, 'dynmm_pack_weight', 'dynmm_wino_pack', 'dynmm_wino43_pack') as spy:
+                with ops.step_scope(prepack=pw):
+                    xg = [t.detach().requires_grad_(True) for t in xs]
+                    ys = [ops.conv2d(t, w, None, 1, (0, 1)) for t in xg]
+                    out.append([t.detach() for t in ys] + list(torch.autograd.grad(ys, xg + [w], gys)))
+            packs.append(sum(spy.count.values()))
+            with torch.no_grad():
+                w.mul_(0.5)                                  # (the optimizer's part: the second step reads other weights)
+        torch.cuda.synchronize()
+        return w, out, packs
+    pw = ops.PackedWeights()
+    w, got, packs = run(pw)
+    _, ref, ref_packs = run(None)
+    assert packs == [4, 0] and ref_packs == [4, 4], (packs, ref_packs)      # (wino_fwd | fwd) + wino43_dgrad per convolution
+    assert list(pw.reg) == [id(w)] and pw.reg[id(w)].kinds == {'fwd', 'wino_fwd', 'wino43_dgrad'}
+    for a, b in zip(got, ref):
+        assert len(a) == len(b) == 5
+        for t, u in zip(a, b):
+            assert torch.equal(t, u)
+    assert not torch.equal(got[0][0], got[1][0])
+
+
+def test_stride1_and_stride2_winograd_input_gradient_operands_are_distinct_kinds(ops):
+    """ops.PackedWeights: a 3x1 stride-1 weight's 'wino_dgrad' and a 3x1 stride-(2,1) weight's 'wino_dgrad_s2' (the polyphase
+    operand) each equal the per-convolution dynmm_wino_pack with dgrad = 1 / 2, and neither weight answers for the other's kind."""
+    from dynmm_amd import lib as L
+    lib = ops._lib()
+    st = torch.cuda.current_stream().cuda_stream
+    w1, w2 = [torch.nn.Parameter(rnd(64, 64, 3, 1, seed=i).cuda()) for i in (1, 2)]
+    pw = ops.PackedWeights()
+    pw.register(w1, L.ConvGeom(2, 64, 16, 16, 64, 16, 16, 3, 1, 1, 1, 1, 0, 64), ('wino_dgrad',))
+    pw.register(w2, L.ConvGeom(2, 64, 16, 16, 64, 8, 16, 3, 1, 2, 1, 1, 0, 64), ('wino_dgrad_s2',))
+    pw.pack()
+    for w, kind, other, dgrad in ((w1, 'wino_dgrad', 'wino_dgrad_s2', 1), (w2, 'wino_dgrad_s2', 'wino_dgrad', 2)):
+        ref = torch.empty(lib.dynmm_wino_packed_floats(64, 64, 3, 1), device='cuda')
+        L.check(lib.dynmm_wino_pack(w.data_ptr(), ref.data_ptr(), None, 64, 64, 3, 1, dgrad, st), 'wino_pack')
+        assert torch.equal(pw.lookup(w, (kind,))[kind], ref), kind
+        assert pw.lookup(w, (other,)) is None and pw.lookup(w, (kind, other)) is None
+    assert not torch.equal(pw.lookup(w1, ('wino_dgrad',))['wino_dgrad'], pw.lookup(w2, ('wino_dgrad_s2',))['wino_dgrad_s2'])
 
 
 def test_fused_eval_cache_follows_parameter_changes(ops):
