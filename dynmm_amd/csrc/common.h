@@ -124,6 +124,29 @@ __device__ __forceinline__ float act_bwd(float g, float y, int act) {
 static inline bool act_is_smooth(int act) { return act == DYNMM_ACT_SWISH || act == DYNMM_ACT_HSWISH; }
 static inline bool act_is_known(int act) { return act >= DYNMM_ACT_NONE && act <= DYNMM_ACT_HSWISH; }
 
+// eval.py:117-141 for ONE output pixel (oh, ow): the bilinear resize (align_corners=False, scales sh = H / Ho, sw = W / Wo) of
+// the C logit planes xn [C,H,W] and the first-maximum arg-max over classes (v > best from -inf, as torch.argmax).  The one
+// home of this arithmetic: eval_confusion_kernel (loss_opt.hip) counts its result, argmax_resize_kernel (segment.hip) keeps it.
+__device__ __forceinline__ int resize_argmax_px(const float* __restrict__ xn, int C, int H, int W, float sh, float sw, int oh,
+                                                int ow) {
+    float fy = sh * ((float)oh + 0.5f) - 0.5f, fx = sw * ((float)ow + 0.5f) - 0.5f;
+    fy = fy < 0.f ? 0.f : fy;
+    fx = fx < 0.f ? 0.f : fx;
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
+    const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
+    const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+    float best = -INFINITY;
+    int arg = 0;
+    for (int c = 0; c < C; ++c) {
+        const float* pc = xn + (size_t)c * H * W;
+        const float v = ly0 * (lx0 * pc[y0 * W + x0] + lx1 * pc[y0 * W + x1]) +
+                        ly1 * (lx0 * pc[y1 * W + x0] + lx1 * pc[y1 * W + x1]);
+        if (v > best) { best = v; arg = c; }       // first maximum, as torch.argmax
+    }
+    return arg;
+}
+
 // out[i] = sum_s slabs[s][i] (+ an optional second region) in a fixed order: the deterministic tail of every
 // split reduction in the library (conv_igemm.hip).
 void launch_reduce_slabs(const float* slabs, float* out, int n, int nslabs, hipStream_t st,

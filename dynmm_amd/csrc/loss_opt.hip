@@ -251,21 +251,7 @@ __global__ void __launch_bounds__(256) eval_confusion_kernel(const float* __rest
         const int lab = (int)ln[p] - 1;
         if (lab < 0 || lab >= C) continue;
         const int oh = p / Wo, ow = p - oh * Wo;
-        float fy = sh * ((float)oh + 0.5f) - 0.5f, fx = sw * ((float)ow + 0.5f) - 0.5f;
-        fy = fy < 0.f ? 0.f : fy;
-        fx = fx < 0.f ? 0.f : fx;
-        const int y0 = (int)fy, x0 = (int)fx;
-        const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-        const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
-        const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-        float best = -INFINITY;
-        int arg = 0;
-        for (int c = 0; c < C; ++c) {
-            const float* pc = xn + (size_t)c * H * W;
-            const float v = ly0 * (lx0 * pc[y0 * W + x0] + lx1 * pc[y0 * W + x1]) +
-                            ly1 * (lx0 * pc[y1 * W + x0] + lx1 * pc[y1 * W + x1]);
-            if (v > best) { best = v; arg = c; }       // first maximum, as torch.argmax
-        }
+        const int arg = resize_argmax_px(xn, C, H, W, sh, sw, oh, ow);       // common.h, shared with segment.hip
         atomicAdd(&cm[(size_t)lab * C + arg], 1ull);
     }
 }

@@ -511,6 +511,7 @@ class InferStep:
 
     `step(rgb, depth, return_weight=False)` returns what `model(rgb, depth, test=True[, return_weight=True])` returns under
     `torch.no_grad()` in eval mode — bit-identical (tests/test_engine.py) — as STATIC tensors: valid until the next call.
+    `step.segment(rgb, depth, return_weight=False)` does the same for `model.segment`: the uint8 label map (tests/test_segment.py).
 
     Two graphs per forward of a gated model (nn/net.py forward_front / forward_back): the front (stems, stem fusion, gate head,
     device side of the compaction decision) and, after the ONE 16-byte host read a compacted hard-gate forward needs
@@ -569,10 +570,12 @@ class InferStep:
                 float(getattr(m, 'temp', 0.0)), bool(getattr(m, 'compact', False)), bool(getattr(m, 'dual_stream', False)),
                 None if bo is None else tuple(bo))
 
-    def _eager(self, rgb, depth, return_weight):
+    def _eager(self, rgb, depth, return_weight, labels=False):
         self.replays['eager'] += 1
         self.launch = 'eager'
         m = self.model
+        if labels:
+            return m.segment(rgb, depth, return_weight=return_weight)
         if hasattr(m, 'hard_gate') or hasattr(m, 'block_rule'):
             return m(rgb, depth, True, True) if return_weight else m(rgb, depth, True)
         return m(rgb, depth)
@@ -593,8 +596,24 @@ class InferStep:
         return graph, out
 
     # ---- call -----------------------------------------------------------------------------------
-    @torch.no_grad()
     def __call__(self, rgb, depth, return_weight=False):
+        return self._run(rgb, depth, return_weight, False)
+
+    def segment(self, rgb, depth, return_weight=False):
+        """The uint8 [N,H,W] label map (and the gate weights with `return_weight`; None where the model has no gate) of
+        `model.segment(rgb, depth)` through the same front / back replays as `__call__`.  "labels" is part of both graph keys:
+        captures of the two kinds coexist on one InferStep, each with its own static result.  Honours `policy='auto'`."""
+        if self.model.training:
+            raise RuntimeError('InferStep.segment needs the model in eval mode (label maps exist at inference only)')
+        dec = self.model.decoder
+        prev, dec.emit_labels = dec.emit_labels, True
+        try:
+            return self._run(rgb, depth, return_weight, True)
+        finally:
+            dec.emit_labels = prev
+
+    @torch.no_grad()
+    def _run(self, rgb, depth, return_weight, labels):
         m = self.model
         gated = hasattr(m, 'forward_front')
         # (gate_free: a network without any gate — ESANetOneModality — stays one graph although evaluate() / train.run / eval.run
@@ -604,14 +623,14 @@ class InferStep:
             (getattr(m, 'ini_stage', False) and getattr(m, 'ini_branches', None) is None) or
             (not gated and (hasattr(m, 'hard_gate') or hasattr(m, 'block_rule'))))
         if m.training or host_decisions:
-            return self._eager(rgb, depth, return_weight)
+            return self._eager(rgb, depth, return_weight, labels)
         stamp = self._weights_stamp()
         if stamp != self._stamp:
             self.reset()
             self._stamp = stamp
-        key = self._key(rgb, depth)
+        key = self._key(rgb, depth) + (('labels',) if labels else ())
         if self.policy == 'auto' and self._choice.get(key) == 'eager':
-            return self._eager(rgb, depth, return_weight)
+            return self._eager(rgb, depth, return_weight, labels)
         fe = self._front.get(key)
         if fe is None:
             s_rgb, s_depth = rgb.clone(), depth.clone()
@@ -627,7 +646,7 @@ class InferStep:
         self.replays['front'] += 1
         self.launch = 'hipGraph replay'
         if not gated:
-            return st
+            return (st, None) if labels and return_weight else st
         if getattr(m, 'save_weight_info', False):
             m.weight_list = torch.cat((m.weight_list, st['weight'].detach().cpu()))
         counts = m.stage_counts(st)                   # (the one host read of a compacted data-dependent forward)
@@ -691,7 +710,8 @@ def _dist_world(group=None):
 
 
 @torch.no_grad()
-def evaluate(model, batches, num_classes=40, hard=True, class_weight=None, shard=True, group=None, losses=None, infer_step=None):
+def evaluate(model, batches, num_classes=40, hard=True, class_weight=None, shard=True, group=None, losses=None, infer_step=None,
+             fused_labels=False):
     """batches: iterable of (rgb, depth, label_orig[N,H0,W0] with 0 = void[, label[N,H,W] at the network's resolution]).
     Returns (mIoU*100, cm).
 
@@ -704,7 +724,11 @@ def evaluate(model, batches, num_classes=40, hard=True, class_weight=None, shard
 
     `losses` (a dict) + `class_weight`: also accumulate validate()'s two validation losses (train.py:432-440;
     src/utils.py:53-97) from batches that carry the 4th element; the dict receives `sum_weighted`, `weight_sum`,
-    `sum_unweighted`, `pixels` (python floats, summed over ranks)."""
+    `sum_unweighted`, `pixels` (python floats, summed over ranks).
+
+    `fused_labels`: where `losses` is not requested and a batch's labels have the network's output size, the forward ends in
+    the label map (`segment`: the decoder's tail fused with the arg-max, no full-resolution logits) and the confusion counts
+    come from ops.label_confusion; any other batch takes the default path."""
     was_training = model.training
     model.eval()
     old_hard, model.hard_gate = getattr(model, 'hard_gate', False), hard
@@ -722,6 +746,11 @@ def evaluate(model, batches, num_classes=40, hard=True, class_weight=None, shard
         if i % world != rank:
             continue
         rgb, depth, label = batch[:3]
+        if fused_labels and losses is None and tuple(label.shape[-2:]) == tuple(rgb.shape[-2:]):
+            pred = infer_step.segment(rgb, depth) if infer_step is not None else model.segment(rgb, depth)
+            lab = label if label.dtype == torch.uint8 else label.to(torch.uint8)
+            ops.label_confusion(pred, lab.reshape(pred.shape), cm)
+            continue
         logits = infer_step(rgb, depth) if infer_step is not None else model(rgb, depth, True)
         if losses is not None and cw is not None and len(batch) > 3:
             ops.validation_loss_accumulate(logits, batch[3], cw, acc4)

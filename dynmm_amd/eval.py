@@ -22,7 +22,7 @@ def set_seed(seed):
     torch.manual_seed(seed)
 
 
-def run(args, model, valid_loader, device=None, use_graph=True):
+def run(args, model, valid_loader, device=None, use_graph=True, fused_labels=False):
     """eval.py:63-151 for a model the caller built and ANY loader the caller brings — an iterable of dicts with `image` [N,3,H,W],
     `depth` [N,1,H,W] (normalised as src/preprocessing.py does) and `label_orig` [N,H0,W0] (0 = void), on the host or the device:
     the entry `python -m dynmm_amd.eval` calls with the NYUv2 test split (dynmm_amd.data.NYUv2) or the synthetic set, and the one
@@ -48,7 +48,7 @@ def run(args, model, valid_loader, device=None, use_graph=True):
                 elif (args.mode == 1 and u < 0.33) or (args.mode == 2 and u < 0.66):
                     depth = depth + args.noise * depth.abs().mean() * torch.randn_like(depth)
                 yield image, depth, s['label_orig'].to(device)
-        miou, _ = engine.evaluate(model, batches(), hard=args.hard, infer_step=step)
+        miou, _ = engine.evaluate(model, batches(), hard=args.hard, infer_step=step, fused_labels=fused_labels)
         print(f'Run {r}, mIoU: {miou:0.2f}')
         results.append(miou)
     if hasattr(model, 'end_weight'):
@@ -63,6 +63,9 @@ def main(argv=None):
     p.set_eval_args()
     p.add_argument('--synthetic_samples', type=int, default=8)
     p.add_argument('--no_hip_graph', action='store_true', help='eager launches instead of hipGraph replays of the forward')
+    p.add_argument('--fused_labels', action='store_true',
+                   help='end the forward in the label map (decoder tail fused with the arg-max) where the labels have the '
+                        "network's size")
     args = p.parse_args(argv)
     args.pretrained_on_imagenet = False
     if args.dataset_dir is not None and args.dataset not in ('nyuv2', 'synthetic'):
@@ -77,7 +80,7 @@ def main(argv=None):
     else:
         data = SyntheticRGBD(args.synthetic_samples, args.batch_size_valid or args.batch_size, args.height, args.width,
                              seed=77, device=device)
-    return run(args, model, data, device, use_graph=not args.no_hip_graph)
+    return run(args, model, data, device, use_graph=not args.no_hip_graph, fused_labels=args.fused_labels)
 
 
 if __name__ == '__main__':

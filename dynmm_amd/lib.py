@@ -158,6 +158,9 @@ SIGNATURES = {
     'dynmm_ce2d_valid': (c_i, [c_f] * 4 + [c_i, c_i, c_i, c_f]),
     'dynmm_ce2d_bwd': (c_i, [c_f] * 5 + [c_i, c_i, c_i, c_f]),
     'dynmm_eval_confusion': (c_i, [c_f, c_f, c_f] + [c_i] * 6 + [c_f]),
+    'dynmm_tail_argmax': (c_i, [c_f] * 6 + [c_i] * 5 + [c_f]),
+    'dynmm_argmax_resize': (c_i, [c_f, c_f] + [c_i] * 6 + [c_f]),
+    'dynmm_label_confusion': (c_i, [c_f, c_f, c_f, c_sz, c_i, c_f]),
     'dynmm_batch_gather': (c_i, [c_f, c_f, c_f, c_i, c_sz, c_f]),
     'dynmm_batch_merge': (c_i, [c_f, c_f, c_f, c_f, c_i, c_sz, c_f]),
     'dynmm_add_n': (c_i, [_PP, c_i, c_f, c_sz, c_f]),

@@ -1,5 +1,7 @@
 """ESANet decoder (model.py:244-410): 3 x [ConvBNAct 3x3, n x NonBottleneck1D, side output (train),
 2x upsample (+ skip add with encoder_decoder_fusion='add')], 3x3 classifier, two 2x upsamples."""
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -8,6 +10,21 @@ from .blocks import ConvBNAct, NonBottleneck1D, chain_ok
 
 
 UPSAMPLING_MODES = ('nearest', 'bilinear', 'learned-3x3', 'learned-3x3-zeropad')
+
+
+@contextlib.contextmanager
+def emitting_labels(model):
+    """The scope of one `segment` forward: eval mode required, no_grad, the decoder's `emit_labels` set and restored."""
+    if model.training:
+        raise RuntimeError(f'{type(model).__name__}.segment needs eval mode: label maps exist at inference only '
+                           '(call model.eval() first)')
+    dec = model.decoder
+    prev, dec.emit_labels = dec.emit_labels, True
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        dec.emit_labels = prev
 
 
 class Upsample(nn.Module):
@@ -86,6 +103,10 @@ class Decoder(nn.Module):
         # The fused tail restates 'learned-3x3-zeropad' only: with any other mode the logits are materialised and the
         # loss takes the plain cross-entropy kernels (what TrainStep(fuse_tail=False) runs).
         self.defer_tail = False
+        # segment() of the networks sets this for one eval-mode forward: the decoder returns the uint8 [N,H,W] label map.
+        # The learned modes run the two up-samplings and the arg-max as ONE kernel (ops.tail_argmax, csrc/segment.hip);
+        # 'nearest' / 'bilinear' take the arg-max of exactly the logits the forward returns otherwise.
+        self.emit_labels = False
 
     def forward(self, enc_outs, unpermute=None):
         """unpermute = (index, inverse): the batch arrives in a permuted (branch-sorted, K16) order; the natural
@@ -101,6 +122,12 @@ class Decoder(nn.Module):
             out = ops.batch_permute(out, *unpermute)
         if self.training and self.defer_tail and torch.is_grad_enabled() and self.upsampling_mode == 'learned-3x3-zeropad':
             out = ops.DeferredLogits(self.upsample1(out), self.upsample2.conv)
+        elif self.emit_labels and not self.training:
+            if 'learned-3x3' in self.upsampling_mode:
+                border = 'zero' if self.upsampling_mode == 'learned-3x3-zeropad' else 'replicate'
+                out = ops.tail_argmax(out, self.upsample1.conv, self.upsample2.conv, border)
+            else:
+                out = ops.argmax_resize(self.upsample2(self.upsample1(out)))
         else:
             out = self.upsample2(self.upsample1(out))
         if self.training:

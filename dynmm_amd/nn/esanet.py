@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from .. import ops
 from .blocks import ResNetEncoder, normalize_activation
+from .decoder import emitting_labels
 from .fusion import SqueezeAndExcitation
 from .net import SkipGateESANet, build_decoder_side, check_decoder_options, decoder_skip
 
@@ -142,3 +143,9 @@ class ESANetOneModality(nn.Module):
         out = self.context_module(out)
         out = self.decoder([out, skips[2], skips[1], skips[0]])
         return (out, None) if return_weight else out
+
+    def segment(self, image, depth=None, return_weight=False):
+        """The uint8 [N,H,W] label map of the eval-mode forward (nn/net.py SkipGateESANet.segment); no gate, so
+        `return_weight` gives (labels, None).  Raises in training mode."""
+        with emitting_labels(self):
+            return self.forward(image, depth, True, return_weight)

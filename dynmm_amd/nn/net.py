@@ -16,7 +16,7 @@ import torch.nn as nn
 from .. import ops
 from .blocks import ConvBNAct, ResNetEncoder, conv_bn_act, normalize_activation
 from .context import get_context_module
-from .decoder import UPSAMPLING_MODES, Decoder
+from .decoder import UPSAMPLING_MODES, Decoder, emitting_labels
 from .fusion import SqueezeAndExciteFusionAdd
 
 
@@ -264,6 +264,12 @@ class SkipGateESANet(nn.Module):
             self.weight_list = torch.cat((self.weight_list, st['weight'].detach().cpu()))
         return self.forward_back(st, self.stage_counts(st), test, return_weight)
 
+    def segment(self, rgb, depth, return_weight=False):
+        """The uint8 [N,H,W] label map (class index = arg-max of the logits `self(rgb, depth, True)` returns) of the eval-mode
+        forward, with the gate weights if asked.  The full-resolution logits are not materialised with the learned
+        up-samplings (nn/decoder.py `emit_labels`).  Raises in training mode."""
+        with emitting_labels(self):
+            return self.forward(rgb, depth, True, return_weight)
 
     def _stem_unfused(self, rgb, depth):
         er, ed = self.encoder_rgb, self.encoder_depth

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from .. import ops
 from .blocks import ResNetEncoder, normalize_activation
+from .decoder import emitting_labels
 from .fusion import SqueezeAndExciteFusionAdd, SqueezeAndExciteReweigh
 from .net import build_decoder_side, check_decoder_options, decoder_skip, encoder_stage_pair
 
@@ -221,3 +222,10 @@ class SkipESANet(nn.Module):
                 skips.append(decoder_skip(self, j, fuse))
         out = self.context_module(fuse)
         return self.decoder([out, skips[2], skips[1], skips[0]])
+
+    def segment(self, rgb, depth, return_weight=False):
+        """The uint8 [N,H,W] label map of the eval-mode forward (nn/net.py SkipGateESANet.segment); this forward returns no
+        gate weights, so `return_weight` gives (labels, None).  Raises in training mode."""
+        with emitting_labels(self):
+            out = self.forward(rgb, depth, True)
+        return (out, None) if return_weight else out

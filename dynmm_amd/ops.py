@@ -2551,6 +2551,65 @@ def eval_confusion(logits, label, cm):
     return cm
 
 
+def _no_grad_inputs(what, *ts):
+    """The label-map operators are inference only: no autograd node exists for them."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise L.DynmmHipError(f'{what} is inference only (no gradient): call it under torch.no_grad() or on detached inputs')
+
+
+def tail_argmax(x, up1_conv, up2_conv, border='zero'):
+    """uint8 [N,4H,4W] label map = first-maximum arg-max over channels of up2(up1(x)), the decoder's two learned 2x
+    up-samplings (their depthwise convs up1_conv, up2_conv; border as upsample2x_dw3x3), in ONE kernel: neither the
+    half-resolution map nor the logits are written (csrc/segment.hip).  x [N,C,H,W] is conv_out's output, C <= 64."""
+    if border not in _BORDERS:
+        raise NotImplementedError(f'tail_argmax: border must be one of {_BORDERS}, got {border!r}')
+    lib = _lib()
+    w1, b1, w2, b2 = up1_conv.weight, up1_conv.bias, up2_conv.weight, up2_conv.bias
+    _no_grad_inputs('tail_argmax', x, w1, b1, w2, b2)
+    x, w1, b1, w2, b2 = (_chk(t.detach() if t is not None else None, n)
+                         for t, n in ((x, 'x'), (w1, 'w1'), (b1, 'b1'), (w2, 'w2'), (b2, 'b2')))
+    N, Cc, H, W = x.shape
+    for w, b in ((w1, b1), (w2, b2)):
+        if w.numel() != Cc * 9 or (b is not None and b.numel() != Cc):
+            raise L.DynmmHipError(f'tail_argmax: depthwise 3x3 weights {tuple(w.shape)} do not match {Cc} channels')
+    pred = torch.empty((N, 4 * H, 4 * W), device=x.device, dtype=torch.uint8)
+    L.check(lib.dynmm_tail_argmax(_p(x), _p(w1), _p(b1), _p(w2), _p(b2), pred.data_ptr(), N, Cc, H, W,
+                                  _BORDERS.index(border), _stream()), 'tail_argmax')
+    return pred
+
+
+def argmax_resize(logits, size=None):
+    """uint8 [N,Ho,Wo] = first-maximum arg-max over channels of the bilinear (align_corners=False) resize of logits
+    [N,C,H,W] to size (None: the logits' own size, the plain arg-max) — eval_confusion's pixel with the label kept."""
+    lib = _lib()
+    _no_grad_inputs('argmax_resize', logits)
+    logits = _chk(logits.detach(), 'logits')
+    N, Cc, H, W = logits.shape
+    Ho, Wo = (H, W) if size is None else (int(size[0]), int(size[1]))
+    pred = torch.empty((N, Ho, Wo), device=logits.device, dtype=torch.uint8)
+    L.check(lib.dynmm_argmax_resize(_p(logits), pred.data_ptr(), N, Cc, H, W, Ho, Wo, _stream()), 'argmax_resize')
+    return pred
+
+
+def label_confusion(pred, label, cm):
+    """cm (int64 [C,C], device) += confusion counts of a uint8 label map `pred` (classes 0..C-1) against `label`
+    (1..C, 0 = void; void and labels above C are skipped): eval_confusion's count for a map that already exists."""
+    lib = _lib()
+    for t, name in ((pred, 'pred'), (label, 'label')):
+        if not t.is_cuda or t.dtype != torch.uint8:
+            raise L.DynmmHipError(f'label_confusion: {name} must be a uint8 tensor on a HIP device')
+    if pred.shape != label.shape:
+        raise L.DynmmHipError(f'label_confusion: pred {tuple(pred.shape)} and label {tuple(label.shape)} differ')
+    pred = pred if pred.is_contiguous() else pred.contiguous()
+    label = label if label.is_contiguous() else label.contiguous()
+    Cc = int(round(cm.numel() ** 0.5))
+    if cm.dtype != torch.int64 or not cm.is_contiguous() or Cc * Cc != cm.numel():
+        raise L.DynmmHipError('cm must be a contiguous int64 [C,C] tensor')
+    L.check(lib.dynmm_label_confusion(pred.data_ptr(), label.data_ptr(), cm.data_ptr(), pred.numel(), Cc, _stream()),
+            'label_confusion')
+    return cm
+
+
 def rgbd_aug(rgb, depth, label, params, H, W, depth_mean, depth_std, raw_depth=False, hsv=None, label_down=True):
     """One batch of network inputs from a decoded split held on the device (csrc/rgbd_aug.hip; dynmm_amd/data.py NYUv2):
     rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit (int16 storage of the uint16 millimetres), label [S,H0,W0] uint8;

@@ -540,6 +540,23 @@ int dynmm_up2ce_bwd(const float* x, const float* w, const float* b, const unsign
 int dynmm_eval_confusion(const float* logits, const unsigned char* label, long long* cm,
                          int N, int C, int H, int W, int Ho, int Wo, void* stream);
 
+/* ---- label maps at inference (segment.hip): the arg-max kept instead of counted.  "First maximum" everywhere: v > best
+ * starting from -inf, as dynmm_eval_confusion and torch.argmax.
+ * tail_argmax: x [N,C,H,W] is the un-permuted output of conv_out (C <= 64, else DYNMM_EUNSUPPORTED); (w1 [C,9], b1 [C]) and
+ *   (w2, b2) are the depthwise convs of the decoder's two learned 2x up-samplings (model.py:404-410); border 0 = zero
+ *   padding ('learned-3x3-zeropad'), 1 = replicate ('learned-3x3').  pred uint8 [N,4H,4W] = arg-max over channels of
+ *   up2(up1(x)); neither the half-resolution map nor the logits reach memory.
+ * argmax_resize: pred uint8 [N,Ho,Wo] = arg-max over channels of the bilinear (align_corners=False) resize of
+ *   logits [N,C,H,W] — the per-pixel arithmetic of dynmm_eval_confusion with the label map kept (C <= 64).
+ * label_confusion: cm[(label-1)*C + pred] += 1 over n_pixels pixels for label in 1..C (0 = void and labels above C are
+ *   skipped; pred >= C is skipped too); cm int64 [C*C], accumulated; exact (integer atomics). */
+int dynmm_tail_argmax(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                      unsigned char* pred, int N, int C, int H, int W, int border, void* stream);
+int dynmm_argmax_resize(const float* logits, unsigned char* pred, int N, int C, int H, int W, int Ho, int Wo,
+                        void* stream);
+int dynmm_label_confusion(const unsigned char* pred, const unsigned char* label, long long* cm, size_t n_pixels, int C,
+                          void* stream);
+
 /* ---- gate-decision stream compaction (new: SURVEY.md K16; the reference never skips compute,
  * src/models/model_skip_mod_globalgate.py:276-310) ----
  * gather: dst[i] = src[idx[i]]  (i < n_out);  merge: out[n] = map[n] >= 0 ? sub[map[n]] : base[n].
