@@ -221,6 +221,9 @@ SIGNATURES = {
     'dynmm_prenorm_fwd': (c_i, [c_f] * 8 + [c_i] * 3 + [c_fl, _DP, c_f]),
     'dynmm_prenorm_bwd_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
     'dynmm_prenorm_bwd': (c_i, [c_f] * 10 + [c_i] * 3 + [_DP, c_i, c_f, c_sz, c_f]),
+    'dynmm_attn_long_supported': (c_i, [c_i] * 4),
+    'dynmm_attn_long_fwd': (c_i, [c_f] * 3 + [c_ll] * 3 + [c_f, c_f] + [c_i] * 6 + [_DP, c_f]),
+    'dynmm_attn_long_bwd': (c_i, [c_f] * 4 + [c_ll] * 3 + [c_f] * 5 + [c_ll] * 3 + [c_i] * 6 + [_DP, c_f]),
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 

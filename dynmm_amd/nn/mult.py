@@ -36,7 +36,8 @@ here so that an exported MultiBench state_dict loads strictly; nothing reads the
 reference's HParams.
 
 The modules are parameter containers.  On the HIP path a layer is: the 1x1-convolution GEMMs (ops_seq.linear_bdt), masked
-cross-modal attention (ops_seq.cross_attention / packed_attention, csrc/xattn.hip), and ONE launch per residual connection that
+cross-modal attention (ops_seq.masked_attention / packed_masked_attention: csrc/xattn.hip up to 64 steps, the streaming kernels of
+csrc/attn_long.hip beyond, so the modalities may differ in length), and ONE launch per residual connection that
 returns both `r + dropout(x)` and the LayerNorm that follows it (ops_seq.prenorm_bdt) — the next layer's LN0 or the encoder's
 final layer_norm.  Dropout sites come from ops_seq.new_sites and are named 'embed_q', 'embed_k', 'embed_v', 'attn', 'res1',
 'relu', 'res2' (per encoder, in call order) and 'out' (the head); `.eval()` switches every site off, and then the key / value
@@ -145,7 +146,7 @@ class TransformerEncoderLayer(nn.Module):
         drop = (p_att, site, 'attn')
         if xk is None:
             qkv = S.linear_bdt(y, sa.in_proj_weight, sa.in_proj_bias)
-            a = S.packed_attention(qkv, H, self.attn_mask, drop)
+            a = S.packed_masked_attention(qkv, H, self.attn_mask, drop)
         else:
             ln0 = self.layer_norms[0]
             kn = S.prenorm_bdt(xk, ln0.weight, ln0.bias, ln0.eps, shared=True)
@@ -153,7 +154,7 @@ class TransformerEncoderLayer(nn.Module):
             q = S.linear_bdt(y, sa.rows('in_proj_weight', 0, E), sa.rows('in_proj_bias', 0, E))
             k = S.linear_bdt(kn, sa.rows('in_proj_weight', E, 2 * E), sa.rows('in_proj_bias', E, 2 * E))
             v = S.linear_bdt(vn, sa.rows('in_proj_weight', 2 * E, 3 * E), sa.rows('in_proj_bias', 2 * E, 3 * E))
-            a = S.cross_attention(q, k, v, H, self.attn_mask, drop)
+            a = S.masked_attention(q, k, v, H, self.attn_mask, drop)
         return S.linear_bdt(a, sa.out_proj.weight, sa.out_proj.bias)
 
     def feed_forward(self, y, site):

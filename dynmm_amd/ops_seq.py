@@ -3,7 +3,8 @@
 Activations are [B, D, T] fp32 (the layout the reference feeds its Conv1d after `x.permute([0, 2, 1])`); every Linear
 / Conv1d(k=1) is `linear_bdt` = the implicit-GEMM MFMA convolution of ops.conv2d with H = 1, W = T.  The kernels
 added for this path live in csrc/seq.hip (with MULT's pre-norm plumbing; attention for head dimensions above 32: csrc/attn.hip;
-MULT's masked cross-modal attention and embedding: csrc/xattn.hip).  As everywhere in dynmm_amd there is no CPU / eager fallback.
+MULT's masked cross-modal attention and embedding: csrc/xattn.hip; attention beyond 64 steps: csrc/attn_long.hip).  As everywhere
+in dynmm_amd there is no CPU / eager fallback.
 """
 import ctypes as C
 import itertools
@@ -540,9 +541,15 @@ def mha_wide(qkv, heads, drop=None):
     return _MHAWide.apply(qkv, heads, _probs_drop(qkv, heads, drop))
 
 
+MHA_MAX_T = 64           # csrc/seq.hip: kSeqMaxT, csrc/attn.hip: kAttnMaxT
+
+
 def attention(qkv, heads, drop=None):
-    """The attention core of an encoder layer: mha_core up to head dimension 32 (every model with d_model <= 160 at nhead = 5:
-    the kernel and the launch they always had), mha_wide above it (Transformer(409, 300): dh = 60)."""
+    """The attention core of an encoder layer.  Up to 64 steps: mha_core up to head dimension 32 (every model with
+    d_model <= 160 at nhead = 5: the kernel and the launch they always had), mha_wide above it (Transformer(409, 300): dh = 60).
+    Longer sequences: packed_attention_long without a mask (the streaming kernels of csrc/attn_long.hip; the same dropout site)."""
+    if qkv.shape[2] > MHA_MAX_T:
+        return packed_attention_long(qkv, heads, False, drop)
     dh = qkv.shape[1] // 3 // heads
     return mha_core(qkv, heads, drop) if dh <= MHA_CORE_MAX_DH else mha_wide(qkv, heads, drop)
 
@@ -645,6 +652,107 @@ def packed_attention(qkv, heads, causal, drop=None):
     """cross_attention on qkv [B, 3D, T] (q | k | v along channels, an in_proj's output): masked self-attention."""
     B, _, T = qkv.shape
     return _PackedAttention.apply(qkv, heads, causal, _make_drop(drop, (B * heads, T, T), qkv.device))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# streaming attention for any sequence length (csrc/attn_long.hip): the function and the dropout site of cross_attention, no
+# stored probabilities
+# ---------------------------------------------------------------------------------------------------------------
+def _attn_long_fwd(q, k, v, heads, causal, drop):
+    B, D, Tq = q.shape
+    Tk = k.shape[2]
+    if tuple(k.shape) != (B, D, Tk) or tuple(v.shape) != (B, D, Tk):
+        raise L.DynmmHipError(f'attention_long: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree')
+    out = torch.empty((B, D, Tq), device=q.device, dtype=torch.float32)
+    lse = torch.empty((B * heads, Tq), device=q.device, dtype=torch.float32)
+    L.check(_lib().dynmm_attn_long_fwd(_p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(out), _p(lse), B, D, Tq,
+                                       Tk, heads, causal, _drop_arg(drop), _stream()), 'attn_long_fwd')
+    return out, lse
+
+
+def _attn_long_bwd(g, q, k, v, out, lse, dq, dk, dv, heads, causal, drop):
+    B, D, Tq = q.shape
+    L.check(_lib().dynmm_attn_long_bwd(_p(g), _p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(out), _p(lse),
+                                       _p(dq), _p(dk), _p(dv), _bstride(dq), _bstride(dk), _bstride(dv), B, D, Tq, k.shape[2],
+                                       heads, causal, _drop_arg(drop), _stream()), 'attn_long_bwd')
+
+
+class _AttentionLong(Function):
+    """out [B, D, Tq] of (q [B, D, Tq], k, v [B, D, Tk]); saves its inputs, out and the per-row log-sum-exp [B*heads, Tq] — no
+    probabilities: the backward recomputes them."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, causal, drop=None):
+        q, k, v = _bdt_view(q, 'q'), _bdt_view(k, 'k'), _bdt_view(v, 'v')
+        ctx.drop, ctx.heads, ctx.causal = drop, heads, int(bool(causal))
+        out, lse = _attn_long_fwd(q, k, v, heads, ctx.causal, drop)
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, out, lse = ctx.saved_tensors
+        g = _chk(g, 'grad')
+        dq, dk, dv = (torch.empty(t.shape, device=g.device, dtype=torch.float32) for t in (q, k, v))
+        _attn_long_bwd(g, q, k, v, out, lse, dq, dk, dv, ctx.heads, ctx.causal, ctx.drop)
+        return dq, dk, dv, None, None, None
+
+
+class _PackedAttentionLong(Function):
+    """_AttentionLong on the channel thirds q | k | v of one qkv [B, 3D, T]; the gradient is one [B, 3D, T] tensor."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, causal, drop=None):
+        qkv = _chk(qkv, 'qkv')
+        D = qkv.shape[1] // 3
+        ctx.drop, ctx.heads, ctx.causal = drop, heads, int(bool(causal))
+        out, lse = _attn_long_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], heads, ctx.causal, drop)
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, out, lse = ctx.saved_tensors
+        g = _chk(g, 'grad')
+        D = qkv.shape[1] // 3
+        dqkv = torch.empty_like(qkv)
+        _attn_long_bwd(g, qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], out, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
+                       ctx.heads, ctx.causal, ctx.drop)
+        return dqkv, None, None, None
+
+
+def attention_long(q, k, v, heads, causal, drop=None):
+    """cross_attention's function, arguments and dropout site (name, shape (B*heads, Tq, Tk), indexing, generator decisions) at
+    any lengths and head dimensions up to 64, by an online softmax over 64-key tiles on the fp32 matrix cores: no
+    [B*heads, Tq, Tk] tensor is written in either pass (csrc/attn_long.hip)."""
+    return _AttentionLong.apply(q, k, v, heads, causal,
+                                _make_drop(drop, (q.shape[0] * heads, q.shape[2], k.shape[2]), q.device))
+
+
+def packed_attention_long(qkv, heads, causal, drop=None):
+    """attention_long on qkv [B, 3D, T] (q | k | v along channels, an in_proj's output)."""
+    B, _, T = qkv.shape
+    return _PackedAttentionLong.apply(qkv, heads, causal, _make_drop(drop, (B * heads, T, T), qkv.device))
+
+
+def _xattn_serves(dh, Tq, Tk):
+    """the whole-row kernels of csrc/xattn.hip hold this shape: the path MULT always had"""
+    return dh <= XATTN_MAX_DH and Tq <= XATTN_MAX_T and Tk <= XATTN_MAX_T
+
+
+def masked_attention(q, k, v, heads, causal, drop=None):
+    """MULT's cross-modal attention at any lengths: cross_attention where it serves (dh <= 32, both lengths <= 64), attention_long
+    beyond."""
+    if _xattn_serves(q.shape[1] // heads, q.shape[2], k.shape[2]):
+        return cross_attention(q, k, v, heads, causal, drop)
+    return attention_long(q, k, v, heads, causal, drop)
+
+
+def packed_masked_attention(qkv, heads, causal, drop=None):
+    """MULT's masked self-attention at any length: packed_attention where it serves, packed_attention_long beyond."""
+    if _xattn_serves(qkv.shape[1] // 3 // heads, qkv.shape[2], qkv.shape[2]):
+        return packed_attention(qkv, heads, causal, drop)
+    return packed_attention_long(qkv, heads, causal, drop)
 
 
 class _PosEmbed(Function):

@@ -859,6 +859,28 @@ int dynmm_prenorm_bwd(const float* gy, const float* gs, const float* sum, const 
                       const float* rstd, float* dx, float* dres, float* dgamma, float* dbeta, int B, int D, int T,
                       const dynmm_dropout* drop, int accumulate, float* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Streaming attention for sequences of any length, csrc/attn_long.hip ----
+ * The function and the tensors of dynmm_xattn_fwd / _bwd — q [B, D, Tq], k and v [B, D, Tk] with a batch stride each (floats),
+ * out [B, D, Tq], the same mask rule (causal: key j is visible to query i iff j <= i + |Tk - Tq|) and the same dropout site
+ * (flat query row, chunks of 8 keys: injected flags are the flat [B*heads, Tq, Tk] bytes, the generator draws the decisions
+ * dynmm_xattn_fwd / dynmm_mha_drop_fwd / dynmm_attn_fwd draw for the same seed, offset, step and shape; the backward redraws
+ * them) — computed by an online softmax over key tiles on v_mfma_f32_16x16x4_f32.  NO probabilities are stored: the forward
+ * writes lse [B*heads, Tq] = log sum_j exp(s_ij) over the visible keys of the scaled scores, the backward takes out and lse and
+ * recomputes P = exp(s - lse).  bwd: g [B, D, Tq] -> dq, dk, dv (overwritten) with batch strides of their own; dq is produced by
+ * workgroups that own query tiles, dk / dv by workgroups that own key tiles: no atomics, no workspace, no host synchronisation,
+ * equal inputs give equal bits, and both calls can be captured.
+ * 1 <= D/heads <= 64 and 1 <= Tq, Tk <= 2^24 (dynmm_attn_long_supported = 1), and B * heads * ceil(max(Tq, Tk) / 64) < 2^31
+ * (one workgroup each); outside that DYNMM_EUNSUPPORTED, a malformed call (a null pointer, a non-positive size, D % heads != 0, a
+ * batch stride below D * T, a dropout probability outside [0, 1)) DYNMM_EINVAL, nothing written in either case. */
+int dynmm_attn_long_supported(int D, int Tq, int Tk, int heads);
+int dynmm_attn_long_fwd(const float* q, const float* k, const float* v, long long q_bstride, long long k_bstride,
+                        long long v_bstride, float* out, float* lse, int B, int D, int Tq, int Tk, int heads, int causal,
+                        const dynmm_dropout* drop, void* stream);
+int dynmm_attn_long_bwd(const float* g, const float* q, const float* k, const float* v, long long q_bstride, long long k_bstride,
+                        long long v_bstride, const float* out, const float* lse, float* dq, float* dk, float* dv,
+                        long long dq_bstride, long long dk_bstride, long long dv_bstride, int B, int D, int Tq, int Tk, int heads,
+                        int causal, const dynmm_dropout* drop, void* stream);
+
 /* ---- NYUv2 input pipeline (FusionDynMM/src/preprocessing.py), csrc/rgbd_aug.hip ---- */
 /* One batch of network inputs from decoded samples kept on the device: rgb [S,H0,W0,3] uint8, depth [S,H0,W0] 16-bit,
  * label [S,H0,W0] uint8.  params [N,8] int32 per output sample: {stored index, th, tw, mode, ci, cj, flip, 0}: the stored sample
