@@ -28,72 +28,17 @@
 // injected flags are the flat [B*heads, T, T] bytes and the generator draws what mha_fwd_kernel draws.  A query's eight chunks are
 // drawn ONCE, two by each of its four lanes (chunks g and g + 4; a Philox call is ~900 issue cycles), kept as bits and exchanged
 // with one lane read per tile.
-#include "common.h"
-#include "dropout.h"
-#include "mfma.h"
+#include "attn_tile.h"
 
 namespace dynmm {
 
 constexpr int kAttnMaxT = 64;
 constexpr int kAttnMaxDh = 64;
 
-// Staging of rows 16 w .. 16 w + 15 of a token-major tile [.][DH + 4] from src [channel][T]: wave w's lanes take token
-// 16 w + (lane & 15), channels 4 s + (lane >> 4).  attn_load issues the DH / 4 loads of a lane (clamped addresses, nothing depends
-// on them yet: the loads of ALL the tensors of a kernel are in flight together), attn_store writes the values, or zeros outside
-// (T, dh).  The zeros are made with a bit mask, not a select on the loaded value: a select lets the compiler sink the load into a
-// branch on `t < T`, which is the predicated load this file must not have.
-template <int DH>
-__device__ __forceinline__ void attn_load(const float* __restrict__ src, float (&v)[DH / 4], int dh, int T, int w, int lane) {
-    const int tc = min(16 * w + (lane & 15), T - 1), g = lane >> 4;
-#pragma unroll
-    for (int s = 0; s < DH / 4; ++s) v[s] = src[(size_t)min(4 * s + g, dh - 1) * T + tc];
-}
-__device__ __forceinline__ float attn_keep_if(float v, bool ok) { return __uint_as_float(__float_as_uint(v) & (ok ? ~0u : 0u)); }
-template <int DH>
-__device__ __forceinline__ void attn_store(float* dst, const float (&v)[DH / 4], int dh, int T, int w, int lane, float mul) {
-    constexpr int LD = DH + 4;
-    const int t = 16 * w + (lane & 15), g = lane >> 4;
-#pragma unroll
-    for (int s = 0; s < DH / 4; ++s) dst[t * LD + 4 * s + g] = attn_keep_if(v[s] * mul, t < T && 4 * s + g < dh);
-}
-
-// bits e of byte 0 / 1: the keep decisions of keys 8 g + e / 8 (g + 4) + e of query row `row` (chunks past T: not drawn)
-__device__ __forceinline__ unsigned attn_draw(const DropState& drop, size_t row, int T, int g) {
-    unsigned bits = 0u;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const int j8 = g + 4 * s;
-        if (8 * j8 < T) {
-            float kp[8];
-            drop.row8(row, j8, T, kp);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) bits |= (kp[e] != 0.f ? 1u : 0u) << (8 * s + e);
-        }
-    }
-    return bits;
-}
-
-// the four decisions of keys 16 jt + 4 g + r (bit r) of this lane's query, from the lane that drew their chunk
-__device__ __forceinline__ unsigned attn_keep4(unsigned bits, int jt, int lane) {
-    const int g = lane >> 4;
-    const int chunk = 2 * jt + (g >> 1);
-    const unsigned v = (unsigned)__shfl((int)bits, (lane & 15) + 16 * (chunk & 3), 64);
-    return (v >> (8 * (chunk >> 2) + 4 * (g & 1))) & 0xfu;
-}
-
-__device__ __forceinline__ float attn_query_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float attn_query_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
-
 template <int DH>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                        float* __restrict__ probs, int D, int T, int H, const DropSpec spec) {
-    constexpr int LD = DH + 4, KS = DH / 4, CT = DH / 16;
+    constexpr int KS = AttnShape<DH>::KS, CT = AttnShape<DH>::CT, LD = AttnShape<DH>::LD;
     extern __shared__ __align__(16) float smem[];
     const int nt = (T + 15) >> 4, rows = 16 * nt;
     float* qs = smem;                    // [rows][LD], scaled by 1 / sqrt(dh) (torch scales q before q @ k^T)
@@ -107,12 +52,12 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
     const float* base = qkv + ((size_t)b * 3 * D + (size_t)h * dh) * T;
     if (w < nt) {
         float rq[KS], rk[KS], rv[KS];
-        attn_load<DH>(base, rq, dh, T, w, lane);
-        attn_load<DH>(base + (size_t)D * T, rk, dh, T, w, lane);
-        attn_load<DH>(base + (size_t)2 * D * T, rv, dh, T, w, lane);
-        attn_store<DH>(qs, rq, dh, T, w, lane, rsqrtf((float)dh));
-        attn_store<DH>(ks, rk, dh, T, w, lane, 1.f);
-        attn_store<DH>(vs, rv, dh, T, w, lane, 1.f);
+        attn_load<DH>(base, rq, dh, T, 0, w, lane);
+        attn_load<DH>(base + (size_t)D * T, rk, dh, T, 0, w, lane);
+        attn_load<DH>(base + (size_t)2 * D * T, rv, dh, T, 0, w, lane);
+        attn_store<DH>(qs, rq, dh, T, 0, w, lane, rsqrtf((float)dh));
+        attn_store<DH>(ks, rk, dh, T, 0, w, lane, 1.f);
+        attn_store<DH>(vs, rv, dh, T, 0, w, lane, 1.f);
     }
     __syncthreads();
     if (w >= nt) return;
@@ -190,7 +135,7 @@ template <int DH>
 __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ qkv,
                                                        const float* __restrict__ probs, float* __restrict__ dqkv, int D, int T,
                                                        int H, const DropSpec spec) {
-    constexpr int LD = DH + 4, KS = DH / 4, CT = DH / 16;
+    constexpr int KS = AttnShape<DH>::KS, CT = AttnShape<DH>::CT, LD = AttnShape<DH>::LD;
     constexpr int LP = 68;                                       // [query][key] tiles: 4 (mod 16) as LD
     extern __shared__ __align__(16) float smem[];
     const int nt = (T + 15) >> 4, rows = 16 * nt;
@@ -208,14 +153,14 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const float* __restrict__
     const float* base = qkv + ((size_t)b * 3 * D + (size_t)h * dh) * T;
     if (w < nt) {
         float rq[KS], rk[KS], rv[KS], rg[KS];
-        attn_load<DH>(base, rq, dh, T, w, lane);
-        attn_load<DH>(base + (size_t)D * T, rk, dh, T, w, lane);
-        attn_load<DH>(base + (size_t)2 * D * T, rv, dh, T, w, lane);
-        attn_load<DH>(gout + ((size_t)b * D + (size_t)h * dh) * T, rg, dh, T, w, lane);
-        attn_store<DH>(qs, rq, dh, T, w, lane, 1.f);
-        attn_store<DH>(ks, rk, dh, T, w, lane, 1.f);
-        attn_store<DH>(vs, rv, dh, T, w, lane, 1.f);
-        attn_store<DH>(gs, rg, dh, T, w, lane, 1.f);
+        attn_load<DH>(base, rq, dh, T, 0, w, lane);
+        attn_load<DH>(base + (size_t)D * T, rk, dh, T, 0, w, lane);
+        attn_load<DH>(base + (size_t)2 * D * T, rv, dh, T, 0, w, lane);
+        attn_load<DH>(gout + ((size_t)b * D + (size_t)h * dh) * T, rg, dh, T, 0, w, lane);
+        attn_store<DH>(qs, rq, dh, T, 0, w, lane, 1.f);
+        attn_store<DH>(ks, rk, dh, T, 0, w, lane, 1.f);
+        attn_store<DH>(vs, rv, dh, T, 0, w, lane, 1.f);
+        attn_store<DH>(gs, rg, dh, T, 0, w, lane, 1.f);
     }
     __syncthreads();
     const bool live = w < nt;                                    // (waves past T idle until the second barrier)

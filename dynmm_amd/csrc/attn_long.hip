@@ -29,80 +29,18 @@
 // Dropout: DropState::row8 with row = the flat query row bh * Tq + i and 8-key chunks — the indexing of seq.hip, attn.hip and
 // xattn.hip: injected flags are the flat [B*heads, Tq, Tk] bytes and the generator draws their decisions.  A chunk is drawn once
 // per query and pass and kept as bits (~900 issue cycles per Philox call): in the query-row passes each of a query's four lanes
-// draws chunks g and g + 4 of the tile (attn.hip's attn_draw), in the key-row pass lane l draws the wave's two chunks of query l.
+// draws chunks g and g + 4 of the tile (attn_draw, as in attn.hip), in the key-row pass lane l draws the wave's two chunks of query l.
 //
-// Loads are unconditional on clamped addresses with the value masked afterwards (a bit mask, see attn.hip); only stores are
-// bounded.  (The staging helpers restate attn.hip's attn_load / attn_store with a tile offset; that file's kernels are pinned.)
-#include "common.h"
-#include "dropout.h"
-#include "mfma.h"
+// Loads are unconditional on clamped addresses with the value masked afterwards (a bit mask, attn_keep_if); only stores are
+// bounded.  The tile helpers (attn_load / attn_store, attn_draw / attn_keep4, the query reductions), the mask rule and the host
+// checks are attn_tile.h's.
+#include "attn_tile.h"
 
 namespace dynmm {
 
 constexpr int kAlMaxDh = 64;
 constexpr int kAlMaxT = 1 << 24;          // flat indices are size_t; 64 * (tile index) and i + |Tk - Tq| stay far inside int
 constexpr int kAlTile = 64;               // rows per workgroup and tokens per streamed tile
-
-template <int DH>
-struct AlShape {
-    static constexpr int KS = (DH + 3) / 4;        // k-steps of a product over the channels
-    static constexpr int CT = (DH + 15) / 16;      // 16-channel tiles of a product over tokens
-    static constexpr int LD = 16 * CT + 4;         // 4 (mod 16)
-};
-
-__device__ __forceinline__ float al_keep_if(float v, bool ok) { return __uint_as_float(__float_as_uint(v) & (ok ? ~0u : 0u)); }
-
-// a lane's values of token t0 + 16 w + (lane & 15), channels 4 s + (lane >> 4), from src [channel][T]
-template <int DH>
-__device__ __forceinline__ void al_load(const float* __restrict__ src, float (&v)[AlShape<DH>::KS], int dh, int T, int t0, int w,
-                                        int lane) {
-    const int tc = min(t0 + 16 * w + (lane & 15), T - 1), g = lane >> 4;
-#pragma unroll
-    for (int s = 0; s < AlShape<DH>::KS; ++s) v[s] = src[(size_t)min(4 * s + g, dh - 1) * T + tc];
-}
-// ... into rows 16 w .. 16 w + 15 of a tile [64][LD]: every channel below 16 CT is written, zeros outside (T, dh)
-template <int DH>
-__device__ __forceinline__ void al_store(float* dst, const float (&v)[AlShape<DH>::KS], int dh, int T, int t0, int w, int lane,
-                                         float mul) {
-    constexpr int KS = AlShape<DH>::KS, CT = AlShape<DH>::CT, LD = AlShape<DH>::LD;
-    const int t = 16 * w + (lane & 15), g = lane >> 4;
-#pragma unroll
-    for (int s = 0; s < 4 * CT; ++s)
-        dst[t * LD + 4 * s + g] = s < KS ? al_keep_if(v[s < KS ? s : 0] * mul, t0 + t < T && 4 * s + g < dh) : 0.f;
-}
-
-// bits e of byte 0 / 1: the keep decisions of keys 8 j8 + e of query row `row`, j8 = 8 kt + g / 8 kt + g + 4 (chunks that begin at
-// or past jvis, the end of the query's visible keys, are not drawn)
-__device__ __forceinline__ unsigned al_draw(const DropState& drop, size_t row, int Tk, int kt, int g, int jvis) {
-    unsigned bits = 0u;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const int j8 = 8 * kt + g + 4 * s;
-        if (8 * j8 < jvis) {
-            float kp[8];
-            drop.row8(row, j8, Tk, kp);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) bits |= (kp[e] != 0.f ? 1u : 0u) << (8 * s + e);
-        }
-    }
-    return bits;
-}
-// the four decisions of keys 16 jt + 4 g + r (bit r) of the tile, from the lane of this query that drew their chunk
-__device__ __forceinline__ unsigned al_keep4(unsigned bits, int jt, int lane) {
-    const int g = lane >> 4;
-    const int chunk = 2 * jt + (g >> 1);
-    const unsigned v = (unsigned)__shfl((int)bits, (lane & 15) + 16 * (chunk & 3), 64);
-    return (v >> (8 * (chunk >> 2) + 4 * (g & 1))) & 0xfu;
-}
-
-__device__ __forceinline__ float al_query_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float al_query_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
 
 // delta of this lane's token from the 16 x 16 product of the wave's out and dOut rows: the diagonal element (t, t) sits in
 // register t & 3 of lane t + 16 (t >> 2).  delta is formed by the instruction and operand order that forms dP, so that with ONE
@@ -126,7 +64,7 @@ struct AlArgs {
 template <int DH>
 __global__ void __launch_bounds__(256) al_fwd_kernel(const AlArgs a, float* __restrict__ out, float* __restrict__ lse, int nqt,
                                                      const DropSpec spec) {
-    constexpr int KS = AlShape<DH>::KS, CT = AlShape<DH>::CT, LD = AlShape<DH>::LD;
+    constexpr int KS = AttnShape<DH>::KS, CT = AttnShape<DH>::CT, LD = AttnShape<DH>::LD;
     __shared__ __align__(16) float ks[kAlTile * LD];
     __shared__ __align__(16) float vs[kAlTile * LD];
     const DropState drop(spec);
@@ -142,17 +80,17 @@ __global__ void __launch_bounds__(256) al_fwd_kernel(const AlArgs a, float* __re
     const float* kb = a.k + (size_t)b * a.sk + (size_t)h * dh * Tk;
     const float* vb = a.v + (size_t)b * a.sv + (size_t)h * dh * Tk;
     float rq[KS], rk[KS], rv[KS];
-    al_load<DH>(qb, rq, dh, Tq, q0, w, lane);
-    al_load<DH>(kb, rk, dh, Tk, 0, w, lane);
-    al_load<DH>(vb, rv, dh, Tk, 0, w, lane);
+    attn_load<DH>(qb, rq, dh, Tq, q0, w, lane);
+    attn_load<DH>(kb, rk, dh, Tk, 0, w, lane);
+    attn_load<DH>(vb, rv, dh, Tk, 0, w, lane);
     float qv[KS];                                                // scaled by 1 / sqrt(dh) (torch scales q before q @ k^T)
 #pragma unroll
-    for (int k = 0; k < KS; ++k) qv[k] = al_keep_if(rq[k] * a.scale, 4 * k + g < dh);
+    for (int k = 0; k < KS; ++k) qv[k] = attn_keep_if(rq[k] * a.scale, 4 * k + g < dh);
     const int off = Tk > Tq ? Tk - Tq : Tq - Tk;
     // keys 0 .. n-1 are visible: to the workgroup's last query (jend), the wave's last query (wvis), this lane's query (jvis)
-    const int jend = a.causal ? min(Tk, min(q0 + kAlTile - 1, Tq - 1) + off + 1) : Tk;
-    const int wvis = a.causal ? min(Tk, min(q0 + 16 * w + 15, Tq - 1) + off + 1) : Tk;
-    const int jvis = a.causal ? min(Tk, ic + off + 1) : Tk;
+    const int jend = a.causal ? attn_visible(min(q0 + kAlTile - 1, Tq - 1), off, Tk) : Tk;
+    const int wvis = a.causal ? attn_visible(min(q0 + 16 * w + 15, Tq - 1), off, Tk) : Tk;
+    const int jvis = a.causal ? attn_visible(ic, off, Tk) : Tk;
     const int nkt = (jend + kAlTile - 1) / kAlTile;
     const bool live = q0 + 16 * w < Tq;                          // (a wave past Tq only helps staging)
     const size_t row = (size_t)bh * Tq + ic;                     // the keep flags are [B*H][Tq][Tk]
@@ -165,15 +103,15 @@ __global__ void __launch_bounds__(256) al_fwd_kernel(const AlArgs a, float* __re
     for (int kt = 0; kt < nkt; ++kt) {
         const int j0 = kAlTile * kt;
         __syncthreads();                                         // every wave is done with the previous tile
-        al_store<DH>(ks, rk, dh, Tk, j0, w, lane, 1.f);
-        al_store<DH>(vs, rv, dh, Tk, j0, w, lane, 1.f);
+        attn_store<DH>(ks, rk, dh, Tk, j0, w, lane, 1.f);
+        attn_store<DH>(vs, rv, dh, Tk, j0, w, lane, 1.f);
         __syncthreads();
         if (kt + 1 < nkt) {
-            al_load<DH>(kb, rk, dh, Tk, j0 + kAlTile, w, lane);
-            al_load<DH>(vb, rv, dh, Tk, j0 + kAlTile, w, lane);
+            attn_load<DH>(kb, rk, dh, Tk, j0 + kAlTile, w, lane);
+            attn_load<DH>(vb, rv, dh, Tk, j0 + kAlTile, w, lane);
         }
         if (!(live && j0 < wvis)) continue;
-        const unsigned bits = dropping ? al_draw(drop, row, Tk, kt, g, jvis) : 0u;
+        const unsigned bits = dropping ? attn_draw<true>(drop, row, Tk, 8 * kt + g, jvis) : 0u;
         // S^T[j][i] = sum_c K[j][c] Q[i][c]
         f32x4 s[4];
 #pragma unroll
@@ -191,12 +129,12 @@ __global__ void __launch_bounds__(256) al_fwd_kernel(const AlArgs a, float* __re
                 s[jt][r] = j0 + 16 * jt + 4 * g + r < jvis ? s[jt][r] : -INFINITY;
                 mx = fmaxf(mx, s[jt][r]);
             }
-        mx = al_query_max(mx);                                   // finite from tile 0 on: key 0 is visible to every query
+        mx = attn_query_max(mx);                                   // finite from tile 0 on: key 0 is visible to every query
         const float alpha = expf(m - mx);                        // (tile 0: exp(-inf) = 0)
         float sum = 0.f;
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
-            const unsigned k4 = dropping ? al_keep4(bits, jt, lane) : 0xfu;
+            const unsigned k4 = dropping ? attn_keep4(bits, jt, lane) : 0xfu;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float e = expf(s[jt][r] - mx);
@@ -204,7 +142,7 @@ __global__ void __launch_bounds__(256) al_fwd_kernel(const AlArgs a, float* __re
                 s[jt][r] = ((k4 >> r) & 1u) ? e * drop.inv : 0.f; // dropout acts on the normalised probabilities: linear in e
             }
         }
-        l = l * alpha + al_query_sum(sum);
+        l = l * alpha + attn_query_sum(sum);
         m = mx;
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) o[ct] *= alpha;
@@ -241,7 +179,7 @@ template <int DH>
 __global__ void __launch_bounds__(256) al_bwd_dq_kernel(const AlArgs a, const float* __restrict__ gout,
                                                         const float* __restrict__ out, const float* __restrict__ lse,
                                                         float* __restrict__ dq, size_t sdq, int nqt, const DropSpec spec) {
-    constexpr int KS = AlShape<DH>::KS, CT = AlShape<DH>::CT, LD = AlShape<DH>::LD;
+    constexpr int KS = AttnShape<DH>::KS, CT = AttnShape<DH>::CT, LD = AttnShape<DH>::LD;
     __shared__ __align__(16) float ks[kAlTile * LD];
     __shared__ __align__(16) float vs[kAlTile * LD];
     const DropState drop(spec);
@@ -258,26 +196,26 @@ __global__ void __launch_bounds__(256) al_bwd_dq_kernel(const AlArgs a, const fl
     const float* vb = a.v + (size_t)b * a.sv + (size_t)h * dh * Tk;
     const size_t ooff = ((size_t)b * a.D + (size_t)h * dh) * Tq;
     float rq[KS], rg[KS], ro[KS], rk[KS], rv[KS];
-    al_load<DH>(qb, rq, dh, Tq, q0, w, lane);
-    al_load<DH>(gout + ooff, rg, dh, Tq, q0, w, lane);
-    al_load<DH>(out + ooff, ro, dh, Tq, q0, w, lane);
-    al_load<DH>(kb, rk, dh, Tk, 0, w, lane);
-    al_load<DH>(vb, rv, dh, Tk, 0, w, lane);
+    attn_load<DH>(qb, rq, dh, Tq, q0, w, lane);
+    attn_load<DH>(gout + ooff, rg, dh, Tq, q0, w, lane);
+    attn_load<DH>(out + ooff, ro, dh, Tq, q0, w, lane);
+    attn_load<DH>(kb, rk, dh, Tk, 0, w, lane);
+    attn_load<DH>(vb, rv, dh, Tk, 0, w, lane);
     const size_t row = (size_t)bh * Tq + ic;
     const float lse_i = lse[row];
     float qv[KS], gv[KS];
     f32x4 dd = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
-        qv[k] = al_keep_if(rq[k] * a.scale, 4 * k + g < dh);
-        gv[k] = al_keep_if(rg[k], 4 * k + g < dh);
+        qv[k] = attn_keep_if(rq[k] * a.scale, 4 * k + g < dh);
+        gv[k] = attn_keep_if(rg[k], 4 * k + g < dh);
         dd = mfma_16x16x4(ro[k], gv[k], dd);                     // out (rows) x dOut (columns) of the wave's 16 queries
     }
     const float delta = al_diag(dd, lane);                       // sum_c dOut[c][i] out[c][i]
     const int off = Tk > Tq ? Tk - Tq : Tq - Tk;
-    const int jend = a.causal ? min(Tk, min(q0 + kAlTile - 1, Tq - 1) + off + 1) : Tk;
-    const int wvis = a.causal ? min(Tk, min(q0 + 16 * w + 15, Tq - 1) + off + 1) : Tk;
-    const int jvis = a.causal ? min(Tk, ic + off + 1) : Tk;
+    const int jend = a.causal ? attn_visible(min(q0 + kAlTile - 1, Tq - 1), off, Tk) : Tk;
+    const int wvis = a.causal ? attn_visible(min(q0 + 16 * w + 15, Tq - 1), off, Tk) : Tk;
+    const int jvis = a.causal ? attn_visible(ic, off, Tk) : Tk;
     const int nkt = (jend + kAlTile - 1) / kAlTile;
     const bool live = q0 + 16 * w < Tq;
     const bool dropping = drop.p > 0.f;
@@ -288,15 +226,15 @@ __global__ void __launch_bounds__(256) al_bwd_dq_kernel(const AlArgs a, const fl
     for (int kt = 0; kt < nkt; ++kt) {
         const int j0 = kAlTile * kt;
         __syncthreads();
-        al_store<DH>(ks, rk, dh, Tk, j0, w, lane, 1.f);
-        al_store<DH>(vs, rv, dh, Tk, j0, w, lane, 1.f);
+        attn_store<DH>(ks, rk, dh, Tk, j0, w, lane, 1.f);
+        attn_store<DH>(vs, rv, dh, Tk, j0, w, lane, 1.f);
         __syncthreads();
         if (kt + 1 < nkt) {
-            al_load<DH>(kb, rk, dh, Tk, j0 + kAlTile, w, lane);
-            al_load<DH>(vb, rv, dh, Tk, j0 + kAlTile, w, lane);
+            attn_load<DH>(kb, rk, dh, Tk, j0 + kAlTile, w, lane);
+            attn_load<DH>(vb, rv, dh, Tk, j0 + kAlTile, w, lane);
         }
         if (!(live && j0 < wvis)) continue;
-        const unsigned bits = dropping ? al_draw(drop, row, Tk, kt, g, jvis) : 0u;
+        const unsigned bits = dropping ? attn_draw<true>(drop, row, Tk, 8 * kt + g, jvis) : 0u;
         f32x4 s[4], d[4];
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) s[jt] = d[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -310,7 +248,7 @@ __global__ void __launch_bounds__(256) al_bwd_dq_kernel(const AlArgs a, const fl
                 }
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
-            const unsigned k4 = dropping ? al_keep4(bits, jt, lane) : 0xfu;
+            const unsigned k4 = dropping ? attn_keep4(bits, jt, lane) : 0xfu;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const bool vis = j0 + 16 * jt + 4 * g + r < jvis;
@@ -351,7 +289,7 @@ __global__ void __launch_bounds__(256) al_bwd_dkv_kernel(const AlArgs a, const f
                                                          const float* __restrict__ out, const float* __restrict__ lse,
                                                          float* __restrict__ dk, float* __restrict__ dv, size_t sdk, size_t sdv,
                                                          int nkt, const DropSpec spec) {
-    constexpr int KS = AlShape<DH>::KS, CT = AlShape<DH>::CT, LD = AlShape<DH>::LD;
+    constexpr int KS = AttnShape<DH>::KS, CT = AttnShape<DH>::CT, LD = AttnShape<DH>::LD;
     __shared__ __align__(16) float qs[kAlTile * LD];             // scaled as the forward scaled it: the same scores
     __shared__ __align__(16) float gs[kAlTile * LD];
     __shared__ float lse_s[kAlTile], del_s[kAlTile];
@@ -376,17 +314,17 @@ __global__ void __launch_bounds__(256) al_bwd_dkv_kernel(const AlArgs a, const f
     const int nqt = (Tq + kAlTile - 1) / kAlTile;
     const int qt0 = a.causal ? max(0, k0 - off) / kAlTile : 0;
     float rk[KS], rv[KS], rq[KS], rg[KS], ro[KS];
-    al_load<DH>(kb, rk, dh, Tk, k0, w, lane);
-    al_load<DH>(vb, rv, dh, Tk, k0, w, lane);
-    al_load<DH>(qb, rq, dh, Tq, kAlTile * qt0, w, lane);
-    al_load<DH>(gb, rg, dh, Tq, kAlTile * qt0, w, lane);
-    al_load<DH>(ob, ro, dh, Tq, kAlTile * qt0, w, lane);
+    attn_load<DH>(kb, rk, dh, Tk, k0, w, lane);
+    attn_load<DH>(vb, rv, dh, Tk, k0, w, lane);
+    attn_load<DH>(qb, rq, dh, Tq, kAlTile * qt0, w, lane);
+    attn_load<DH>(gb, rg, dh, Tq, kAlTile * qt0, w, lane);
+    attn_load<DH>(ob, ro, dh, Tq, kAlTile * qt0, w, lane);
     float rl = lb[min(kAlTile * qt0 + 16 * w + li, Tq - 1)];
     float kv[KS], vv[KS];
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
-        kv[k] = al_keep_if(rk[k], 4 * k + g < dh);
-        vv[k] = al_keep_if(rv[k], 4 * k + g < dh);
+        kv[k] = attn_keep_if(rk[k], 4 * k + g < dh);
+        vv[k] = attn_keep_if(rv[k], 4 * k + g < dh);
     }
     const bool live = kmin < Tk;
     const bool dropping = drop.p > 0.f;
@@ -397,12 +335,12 @@ __global__ void __launch_bounds__(256) al_bwd_dkv_kernel(const AlArgs a, const f
     for (int qt = qt0; qt < nqt; ++qt) {
         const int i0 = kAlTile * qt;
         __syncthreads();
-        al_store<DH>(qs, rq, dh, Tq, i0, w, lane, a.scale);
-        al_store<DH>(gs, rg, dh, Tq, i0, w, lane, 1.f);
+        attn_store<DH>(qs, rq, dh, Tq, i0, w, lane, a.scale);
+        attn_store<DH>(gs, rg, dh, Tq, i0, w, lane, 1.f);
         {
             f32x4 dd = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int k = 0; k < KS; ++k) dd = mfma_16x16x4(al_keep_if(rg[k], 4 * k + g < dh), ro[k], dd);
+            for (int k = 0; k < KS; ++k) dd = mfma_16x16x4(attn_keep_if(rg[k], 4 * k + g < dh), ro[k], dd);
             const float dl = al_diag(dd, lane);
             if (g == 0) {
                 lse_s[16 * w + li] = rl;
@@ -411,9 +349,9 @@ __global__ void __launch_bounds__(256) al_bwd_dkv_kernel(const AlArgs a, const f
         }
         __syncthreads();
         if (qt + 1 < nqt) {
-            al_load<DH>(qb, rq, dh, Tq, i0 + kAlTile, w, lane);
-            al_load<DH>(gb, rg, dh, Tq, i0 + kAlTile, w, lane);
-            al_load<DH>(ob, ro, dh, Tq, i0 + kAlTile, w, lane);
+            attn_load<DH>(qb, rq, dh, Tq, i0 + kAlTile, w, lane);
+            attn_load<DH>(gb, rg, dh, Tq, i0 + kAlTile, w, lane);
+            attn_load<DH>(ob, ro, dh, Tq, i0 + kAlTile, w, lane);
             rl = lb[min(i0 + kAlTile + 16 * w + li, Tq - 1)];
         }
         // the tile's last query does not see the wave's first key: nothing of the tile does
@@ -503,10 +441,6 @@ static unsigned al_grid(int B, int heads, int T) {
     return n < (1ull << 31) ? (unsigned)n : 0u;
 }
 
-static bool al_args_ok(int B, int D, int Tq, int Tk, int heads, const dynmm_dropout* drop) {
-    return B > 0 && D > 0 && Tq > 0 && Tk > 0 && heads > 0 && D % heads == 0 && drop_ok(drop);
-}
-
 // the instantiations: dh <= 4 (MULT's cross-modal transformers), <= 16 (its memory transformers: 12), <= 32, <= 64 (ef_tran: 60)
 #define DYNMM_AL_DISPATCH(dh, CALL)          \
     do {                                     \
@@ -520,14 +454,14 @@ extern "C" int dynmm_attn_long_fwd(const float* q, const float* k, const float* 
                                    long long v_bstride, float* out, float* lse, int B, int D, int Tq, int Tk, int heads, int causal,
                                    const dynmm_dropout* drop, void* stream) {
     (void)hipGetLastError();
-    if (!q || !k || !v || !out || !lse || !al_args_ok(B, D, Tq, Tk, heads, drop)) return DYNMM_EINVAL;
-    if (q_bstride < (long long)D * Tq || k_bstride < (long long)D * Tk || v_bstride < (long long)D * Tk) return DYNMM_EINVAL;
+    if (!q || !k || !v || !out || !lse || !attn_args_ok(B, D, Tq, Tk, heads, drop)) return DYNMM_EINVAL;
+    if (!attn_bstrides_ok(D, Tq, Tk, q_bstride, k_bstride, v_bstride)) return DYNMM_EINVAL;
     const unsigned nq = al_grid(B, heads, Tq);
     if (!dynmm_attn_long_supported(D, Tq, Tk, heads) || !nq) return DYNMM_EUNSUPPORTED;
     const DropSpec spec = drop_spec(drop);
     const int dh = D / heads;
     const AlArgs a{q, k, v, (size_t)q_bstride, (size_t)k_bstride, (size_t)v_bstride, D, Tq, Tk, heads, causal ? 1 : 0,
-                   (float)(1.0 / sqrt((double)dh))};
+                   attn_scale(dh)};
 #define DYNMM_AL_F(DH) hipLaunchKernelGGL((al_fwd_kernel<DH>), dim3(nq), dim3(256), 0, ST, a, out, lse, ceil_div(Tq, kAlTile), spec)
     DYNMM_AL_DISPATCH(dh, DYNMM_AL_F);
 #undef DYNMM_AL_F
@@ -540,16 +474,16 @@ extern "C" int dynmm_attn_long_bwd(const float* g, const float* q, const float* 
                                    float* dk, float* dv, long long dq_bstride, long long dk_bstride, long long dv_bstride, int B,
                                    int D, int Tq, int Tk, int heads, int causal, const dynmm_dropout* drop, void* stream) {
     (void)hipGetLastError();
-    if (!g || !q || !k || !v || !out || !lse || !dq || !dk || !dv || !al_args_ok(B, D, Tq, Tk, heads, drop)) return DYNMM_EINVAL;
-    if (q_bstride < (long long)D * Tq || k_bstride < (long long)D * Tk || v_bstride < (long long)D * Tk ||
-        dq_bstride < (long long)D * Tq || dk_bstride < (long long)D * Tk || dv_bstride < (long long)D * Tk)
+    if (!g || !q || !k || !v || !out || !lse || !dq || !dk || !dv || !attn_args_ok(B, D, Tq, Tk, heads, drop)) return DYNMM_EINVAL;
+    if (!attn_bstrides_ok(D, Tq, Tk, q_bstride, k_bstride, v_bstride) ||
+        !attn_bstrides_ok(D, Tq, Tk, dq_bstride, dk_bstride, dv_bstride))
         return DYNMM_EINVAL;
     const unsigned nq = al_grid(B, heads, Tq), nk = al_grid(B, heads, Tk);
     if (!dynmm_attn_long_supported(D, Tq, Tk, heads) || !nq || !nk) return DYNMM_EUNSUPPORTED;
     const DropSpec spec = drop_spec(drop);
     const int dh = D / heads;
     const AlArgs a{q, k, v, (size_t)q_bstride, (size_t)k_bstride, (size_t)v_bstride, D, Tq, Tk, heads, causal ? 1 : 0,
-                   (float)(1.0 / sqrt((double)dh))};
+                   attn_scale(dh)};
 #define DYNMM_AL_B(DH)                                                                                                         \
     do {                                                                                                                       \
         hipLaunchKernelGGL((al_bwd_dq_kernel<DH>), dim3(nq), dim3(256), 0, ST, a, g, out, lse, dq, (size_t)dq_bstride,         \

@@ -4,8 +4,7 @@
 //   * the embedding dropout(scale x + pos(x)) with the padding rule, one or two dropout sites per launch (dynmm_posembed_*).
 // The pre-norm layer's `r + dropout(x)` fused with the LayerNorm that follows it (dynmm_prenorm_*) runs on seq.hip's LayerNorm
 // kernels.  DESIGN.md section 7m.
-#include "common.h"
-#include "dropout.h"
+#include "attn_tile.h"
 
 namespace dynmm {
 
@@ -81,7 +80,7 @@ __global__ void __launch_bounds__(64) xattn_fwd_kernel(const float* __restrict__
     }
     __syncthreads();
     const int off = Tk > Tq ? Tk - Tq : Tq - Tk;
-    const int jmax = actq ? (causal ? min(Tk, i + off + 1) : Tk) : 0;    // keys 0 .. jmax-1 are visible to query i
+    const int jmax = actq ? (causal ? attn_visible(i, off, Tk) : Tk) : 0;    // keys 0 .. jmax-1 are visible to query i
     const size_t row = (size_t)blockIdx.x * Tq + i;                  // probs and their keep flags are [B*H][Tq][Tk]
     float* pr = ps + iq * ld;
     // pass 1: the row maximum of the raw scores, as (hi, lo); the scores are recomputed in pass 2 instead of stored
@@ -186,7 +185,7 @@ __global__ void __launch_bounds__(64) xattn_bwd_kernel(const float* __restrict__
         if (i < Tk) ps[r * ld + i] = pg[(size_t)r * Tk + i];
     __syncthreads();
     const int off = Tk > Tq ? Tk - Tq : Tq - Tk;
-    const int jmax = actq ? (causal ? min(Tk, i + off + 1) : Tk) : 0;
+    const int jmax = actq ? (causal ? attn_visible(i, off, Tk) : Tk) : 0;
     const size_t row = (size_t)blockIdx.x * Tq + i;
     float* pr = ps + iq * ld;
     float* dr = ds + iq * ld;
@@ -339,17 +338,10 @@ using namespace dynmm;
 
 #define ST ((hipStream_t)stream)
 
-static bool xattn_args_ok(int B, int D, int Tq, int Tk, int heads, const dynmm_dropout* drop) {
-    return B > 0 && D > 0 && Tq > 0 && Tk > 0 && heads > 0 && D % heads == 0 && drop_ok(drop);
-}
-
 extern "C" int dynmm_xattn_supported(int D, int Tq, int Tk, int heads) {
     if (D <= 0 || Tq <= 0 || Tk <= 0 || heads <= 0 || D % heads != 0) return 0;
     return (D / heads <= kXaMaxDh && Tq <= kXaMaxT && Tk <= kXaMaxT) ? 1 : 0;
 }
-
-// 1 / sqrt(dh), correctly rounded (the device's reciprocal square root is not)
-static float xattn_scale(int dh) { return (float)(1.0 / sqrt((double)dh)); }
 
 static size_t xattn_lds(int DH, int Tq, int Tk, bool bwd) {
     const size_t ld = (size_t)(Tk | 1);
@@ -370,14 +362,14 @@ extern "C" int dynmm_xattn_fwd(const float* q, const float* k, const float* v, l
                                long long v_bstride, float* out, float* probs, int B, int D, int Tq, int Tk, int heads,
                                int causal, const dynmm_dropout* drop, void* stream) {
     (void)hipGetLastError();
-    if (!q || !k || !v || !out || !probs || !xattn_args_ok(B, D, Tq, Tk, heads, drop)) return DYNMM_EINVAL;
-    if (q_bstride < (long long)D * Tq || k_bstride < (long long)D * Tk || v_bstride < (long long)D * Tk) return DYNMM_EINVAL;
+    if (!q || !k || !v || !out || !probs || !attn_args_ok(B, D, Tq, Tk, heads, drop)) return DYNMM_EINVAL;
+    if (!attn_bstrides_ok(D, Tq, Tk, q_bstride, k_bstride, v_bstride)) return DYNMM_EINVAL;
     if (!dynmm_xattn_supported(D, Tq, Tk, heads)) return DYNMM_EUNSUPPORTED;
     const DropSpec spec = drop_spec(drop);
     const int dh = D / heads;
 #define DYNMM_XA_F(DH, EX) hipLaunchKernelGGL((xattn_fwd_kernel<DH, EX>), dim3(B * heads), dim3(64), xattn_lds(DH, Tq, Tk, false), \
                                               ST, q, k, v, (size_t)q_bstride, (size_t)k_bstride, (size_t)v_bstride, out, probs, D, \
-                                              Tq, Tk, heads, causal ? 1 : 0, xattn_scale(dh), spec)
+                                              Tq, Tk, heads, causal ? 1 : 0, attn_scale(dh), spec)
     DYNMM_XA_DISPATCH(dh, DYNMM_XA_F);
 #undef DYNMM_XA_F
     DYNMM_LAUNCH_CHECK();
@@ -389,9 +381,9 @@ extern "C" int dynmm_xattn_bwd(const float* g, const float* q, const float* k, c
                                long long dq_bstride, long long dk_bstride, long long dv_bstride, int B, int D, int Tq, int Tk,
                                int heads, int causal, const dynmm_dropout* drop, void* stream) {
     (void)hipGetLastError();
-    if (!g || !q || !k || !v || !probs || !dq || !dk || !dv || !xattn_args_ok(B, D, Tq, Tk, heads, drop)) return DYNMM_EINVAL;
-    if (q_bstride < (long long)D * Tq || k_bstride < (long long)D * Tk || v_bstride < (long long)D * Tk ||
-        dq_bstride < (long long)D * Tq || dk_bstride < (long long)D * Tk || dv_bstride < (long long)D * Tk)
+    if (!g || !q || !k || !v || !probs || !dq || !dk || !dv || !attn_args_ok(B, D, Tq, Tk, heads, drop)) return DYNMM_EINVAL;
+    if (!attn_bstrides_ok(D, Tq, Tk, q_bstride, k_bstride, v_bstride) ||
+        !attn_bstrides_ok(D, Tq, Tk, dq_bstride, dk_bstride, dv_bstride))
         return DYNMM_EINVAL;
     if (!dynmm_xattn_supported(D, Tq, Tk, heads)) return DYNMM_EUNSUPPORTED;
     const DropSpec spec = drop_spec(drop);
@@ -399,7 +391,7 @@ extern "C" int dynmm_xattn_bwd(const float* g, const float* q, const float* k, c
 #define DYNMM_XA_B(DH, EX) hipLaunchKernelGGL((xattn_bwd_kernel<DH, EX>), dim3(B * heads), dim3(64), xattn_lds(DH, Tq, Tk, true), \
                                               ST, g, q, k, v, (size_t)q_bstride, (size_t)k_bstride, (size_t)v_bstride, probs, dq, \
                                               dk, dv, (size_t)dq_bstride, (size_t)dk_bstride, (size_t)dv_bstride, D, Tq, Tk, \
-                                              heads, causal ? 1 : 0, xattn_scale(dh), spec)
+                                              heads, causal ? 1 : 0, attn_scale(dh), spec)
     DYNMM_XA_DISPATCH(dh, DYNMM_XA_B);
 #undef DYNMM_XA_B
     DYNMM_LAUNCH_CHECK();

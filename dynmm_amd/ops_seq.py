@@ -8,6 +8,7 @@ in dynmm_amd there is no CPU / eager fallback.
 """
 import ctypes as C
 import itertools
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function
@@ -488,6 +489,12 @@ def lrtf(zs, factors, fusion_weights, fusion_bias):
     return _LRTF.apply(w, bias, M, *zs, *factors)
 
 
+def _probs_shape(heads, q, k=None):
+    """(B*heads, Tq, Tk): the attention probabilities of q [B, ., Tq] on k [B, ., Tk] (None: on q itself) — the shape of their
+    dropout site, whether or not a tensor of them exists"""
+    return (q.shape[0] * heads, q.shape[2], (q if k is None else k).shape[2])
+
+
 def _mha_function(name, fwd, bwd, fwd_label, bwd_label, doc=None):
     """The autograd Function of an attention core: out [B, D, T] of (qkv [B, 3D, T], heads, drop) through the library's entry
     points `fwd` / `bwd`, which share one argument list."""
@@ -497,7 +504,7 @@ def _mha_function(name, fwd, bwd, fwd_label, bwd_label, doc=None):
         B, D3, T = qkv.shape
         D = D3 // 3
         out = torch.empty((B, D, T), device=qkv.device, dtype=torch.float32)
-        probs = torch.empty((B * heads, T, T), device=qkv.device, dtype=torch.float32)
+        probs = torch.empty(_probs_shape(heads, qkv), device=qkv.device, dtype=torch.float32)
         L.check(getattr(_lib(), fwd)(_p(qkv), _p(out), _p(probs), B, D, T, heads, _drop_arg(drop), _stream()), fwd_label)
         ctx.drop = drop
         ctx.save_for_backward(qkv, probs)
@@ -526,7 +533,7 @@ MHA_CORE_MAX_DH = 32     # csrc/seq.hip: kSeqMaxDh
 
 def _probs_drop(qkv, heads, drop):
     """the Drop of the [B*heads, T, T] attention probabilities; drop = (p, site, name) or None"""
-    return _make_drop(drop, (qkv.shape[0] * heads, qkv.shape[2], qkv.shape[2]), qkv.device)
+    return _make_drop(drop, _probs_shape(heads, qkv), qkv.device)
 
 
 def mha_core(qkv, heads, drop=None):
@@ -576,66 +583,75 @@ def _bstride(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2]
 
 
-def _xattn_fwd(q, k, v, heads, causal, drop):
+# A family of kernels over separate q, k, v: `op` names it in messages, dynmm_<stem>_fwd / _bwd are its entry points (one argument
+# list up to what the forward saves), extra(heads, q, k) is the shape of the one tensor the forward writes beside `out`, and
+# saves_out says whether the backward reads `out` in front of it.
+_QKVFamily = namedtuple('_QKVFamily', 'op stem extra saves_out')
+_XATTN = _QKVFamily('cross_attention', 'xattn', _probs_shape, False)                                   # the probabilities
+_ATTN_LONG = _QKVFamily('attention_long', 'attn_long', lambda heads, q, k: _probs_shape(heads, q, k)[:2], True)   # out, lse
+
+
+def _qkv_fwd(fam, q, k, v, heads, causal, drop):
+    """(out, what the backward needs beside the inputs) of one forward launch of the family"""
     B, D, Tq = q.shape
     Tk = k.shape[2]
     if tuple(k.shape) != (B, D, Tk) or tuple(v.shape) != (B, D, Tk):
-        raise L.DynmmHipError(f'cross_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree')
+        raise L.DynmmHipError(f'{fam.op}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree')
     out = torch.empty((B, D, Tq), device=q.device, dtype=torch.float32)
-    probs = torch.empty((B * heads, Tq, Tk), device=q.device, dtype=torch.float32)
-    L.check(_lib().dynmm_xattn_fwd(_p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(out), _p(probs), B, D, Tq, Tk,
-                                   heads, causal, _drop_arg(drop), _stream()), 'xattn_fwd')
-    return out, probs
+    extra = torch.empty(fam.extra(heads, q, k), device=q.device, dtype=torch.float32)
+    L.check(getattr(_lib(), f'dynmm_{fam.stem}_fwd')(_p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(out), _p(extra),
+                                                    B, D, Tq, Tk, heads, causal, _drop_arg(drop), _stream()), f'{fam.stem}_fwd')
+    return out, ((out, extra) if fam.saves_out else (extra,))
 
 
-def _xattn_bwd(g, q, k, v, probs, dq, dk, dv, heads, causal, drop):
+def _qkv_bwd(fam, g, q, k, v, saved, dq, dk, dv, heads, causal, drop):
     B, D, Tq = q.shape
-    L.check(_lib().dynmm_xattn_bwd(_p(g), _p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(probs), _p(dq), _p(dk),
-                                   _p(dv), _bstride(dq), _bstride(dk), _bstride(dv), B, D, Tq, k.shape[2], heads, causal,
-                                   _drop_arg(drop), _stream()), 'xattn_bwd')
+    L.check(getattr(_lib(), f'dynmm_{fam.stem}_bwd')(_p(g), _p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v),
+                                                    *map(_p, saved), _p(dq), _p(dk), _p(dv), _bstride(dq), _bstride(dk),
+                                                    _bstride(dv), B, D, Tq, k.shape[2], heads, causal, _drop_arg(drop), _stream()),
+            f'{fam.stem}_bwd')
 
 
-class _CrossAttention(Function):
-    """out [B, D, Tq] of (q [B, D, Tq], k, v [B, D, Tk]); saves its inputs and the probabilities before dropout."""
+def _thirds(t):
+    """the channel thirds q | k | v of a packed [B, 3D, T] (views)"""
+    D = t.shape[1] // 3
+    return t[:, :D], t[:, D:2 * D], t[:, 2 * D:]
 
-    @staticmethod
-    def forward(ctx, q, k, v, heads, causal, drop=None):
-        q, k, v = _bdt_view(q, 'q'), _bdt_view(k, 'k'), _bdt_view(v, 'v')
+
+def _qkv_function(name, fam, packed, doc):
+    """The autograd Function of a q / k / v family: out [B, D, Tq] of (q, k, v, heads, causal, drop=None), or with `packed` of
+    (qkv, heads, causal, drop=None), whose gradient is then one [B, 3D, T] tensor."""
+    n = 1 if packed else 3
+
+    def forward(ctx, *args):
+        inputs, (heads, causal, drop) = args[:n], (args[n:] + (None,))[:3]
+        inputs = (_chk(inputs[0], 'qkv'),) if packed else tuple(_bdt_view(t, c) for t, c in zip(inputs, 'qkv'))
         ctx.drop, ctx.heads, ctx.causal = drop, heads, int(bool(causal))
-        out, probs = _xattn_fwd(q, k, v, heads, ctx.causal, drop)
-        ctx.save_for_backward(q, k, v, probs)
+        out, saved = _qkv_fwd(fam, *(_thirds(inputs[0]) if packed else inputs), heads, ctx.causal, drop)
+        ctx.save_for_backward(*inputs, *saved)
         return out
 
-    @staticmethod
     def backward(ctx, g):
-        q, k, v, probs = ctx.saved_tensors
+        inputs, saved = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
         g = _chk(g, 'grad')
-        dq, dk, dv = (torch.empty(t.shape, device=g.device, dtype=torch.float32) for t in (q, k, v))
-        _xattn_bwd(g, q, k, v, probs, dq, dk, dv, ctx.heads, ctx.causal, ctx.drop)
-        return dq, dk, dv, None, None, None
+        if packed:
+            grads = (torch.empty_like(inputs[0]),)
+            inputs, parts = _thirds(inputs[0]), _thirds(grads[0])
+        else:
+            grads = parts = tuple(torch.empty(t.shape, device=g.device, dtype=torch.float32) for t in inputs)
+        _qkv_bwd(fam, g, *inputs, saved, *parts, ctx.heads, ctx.causal, ctx.drop)
+        return (*grads, None, None, None)
+
+    return type(name, (Function,), {'forward': staticmethod(forward), 'backward': staticmethod(backward), '__doc__': doc,
+                                    '__module__': __name__})
 
 
-class _PackedAttention(Function):
-    """_CrossAttention on the channel thirds q | k | v of one qkv [B, 3D, T]; the gradient is one [B, 3D, T] tensor."""
-
-    @staticmethod
-    def forward(ctx, qkv, heads, causal, drop=None):
-        qkv = _chk(qkv, 'qkv')
-        D = qkv.shape[1] // 3
-        ctx.drop, ctx.heads, ctx.causal = drop, heads, int(bool(causal))
-        out, probs = _xattn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], heads, ctx.causal, drop)
-        ctx.save_for_backward(qkv, probs)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        qkv, probs = ctx.saved_tensors
-        g = _chk(g, 'grad')
-        D = qkv.shape[1] // 3
-        dqkv = torch.empty_like(qkv)
-        _xattn_bwd(g, qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], probs, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
-                   ctx.heads, ctx.causal, ctx.drop)
-        return dqkv, None, None, None
+_CrossAttention = _qkv_function(
+    '_CrossAttention', _XATTN, False,
+    "out [B, D, Tq] of (q [B, D, Tq], k, v [B, D, Tk]); saves its inputs and the probabilities before dropout.")
+_PackedAttention = _qkv_function(
+    '_PackedAttention', _XATTN, True,
+    "_CrossAttention on the channel thirds q | k | v of one qkv [B, 3D, T]; the gradient is one [B, 3D, T] tensor.")
 
 
 def cross_attention(q, k, v, heads, causal, drop=None):
@@ -644,95 +660,37 @@ def cross_attention(q, k, v, heads, causal, drop=None):
     slices of one packed [B, 3D, T] tensor (no copy; `packed_attention` also returns their gradient as one tensor).
     drop = (p, site, name) or None: dropout on the [B*heads, Tq, Tk] probabilities.  Head dimensions up to 32, lengths up to 64
     (csrc/xattn.hip)."""
-    return _CrossAttention.apply(q, k, v, heads, causal,
-                                 _make_drop(drop, (q.shape[0] * heads, q.shape[2], k.shape[2]), q.device))
+    return _CrossAttention.apply(q, k, v, heads, causal, _make_drop(drop, _probs_shape(heads, q, k), q.device))
 
 
 def packed_attention(qkv, heads, causal, drop=None):
     """cross_attention on qkv [B, 3D, T] (q | k | v along channels, an in_proj's output): masked self-attention."""
-    B, _, T = qkv.shape
-    return _PackedAttention.apply(qkv, heads, causal, _make_drop(drop, (B * heads, T, T), qkv.device))
+    return _PackedAttention.apply(qkv, heads, causal, _probs_drop(qkv, heads, drop))
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # streaming attention for any sequence length (csrc/attn_long.hip): the function and the dropout site of cross_attention, no
 # stored probabilities
 # ---------------------------------------------------------------------------------------------------------------
-def _attn_long_fwd(q, k, v, heads, causal, drop):
-    B, D, Tq = q.shape
-    Tk = k.shape[2]
-    if tuple(k.shape) != (B, D, Tk) or tuple(v.shape) != (B, D, Tk):
-        raise L.DynmmHipError(f'attention_long: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not agree')
-    out = torch.empty((B, D, Tq), device=q.device, dtype=torch.float32)
-    lse = torch.empty((B * heads, Tq), device=q.device, dtype=torch.float32)
-    L.check(_lib().dynmm_attn_long_fwd(_p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(out), _p(lse), B, D, Tq,
-                                       Tk, heads, causal, _drop_arg(drop), _stream()), 'attn_long_fwd')
-    return out, lse
-
-
-def _attn_long_bwd(g, q, k, v, out, lse, dq, dk, dv, heads, causal, drop):
-    B, D, Tq = q.shape
-    L.check(_lib().dynmm_attn_long_bwd(_p(g), _p(q), _p(k), _p(v), _bstride(q), _bstride(k), _bstride(v), _p(out), _p(lse),
-                                       _p(dq), _p(dk), _p(dv), _bstride(dq), _bstride(dk), _bstride(dv), B, D, Tq, k.shape[2],
-                                       heads, causal, _drop_arg(drop), _stream()), 'attn_long_bwd')
-
-
-class _AttentionLong(Function):
+_AttentionLong = _qkv_function(
+    '_AttentionLong', _ATTN_LONG, False,
     """out [B, D, Tq] of (q [B, D, Tq], k, v [B, D, Tk]); saves its inputs, out and the per-row log-sum-exp [B*heads, Tq] — no
-    probabilities: the backward recomputes them."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, heads, causal, drop=None):
-        q, k, v = _bdt_view(q, 'q'), _bdt_view(k, 'k'), _bdt_view(v, 'v')
-        ctx.drop, ctx.heads, ctx.causal = drop, heads, int(bool(causal))
-        out, lse = _attn_long_fwd(q, k, v, heads, ctx.causal, drop)
-        ctx.save_for_backward(q, k, v, out, lse)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        q, k, v, out, lse = ctx.saved_tensors
-        g = _chk(g, 'grad')
-        dq, dk, dv = (torch.empty(t.shape, device=g.device, dtype=torch.float32) for t in (q, k, v))
-        _attn_long_bwd(g, q, k, v, out, lse, dq, dk, dv, ctx.heads, ctx.causal, ctx.drop)
-        return dq, dk, dv, None, None, None
-
-
-class _PackedAttentionLong(Function):
-    """_AttentionLong on the channel thirds q | k | v of one qkv [B, 3D, T]; the gradient is one [B, 3D, T] tensor."""
-
-    @staticmethod
-    def forward(ctx, qkv, heads, causal, drop=None):
-        qkv = _chk(qkv, 'qkv')
-        D = qkv.shape[1] // 3
-        ctx.drop, ctx.heads, ctx.causal = drop, heads, int(bool(causal))
-        out, lse = _attn_long_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], heads, ctx.causal, drop)
-        ctx.save_for_backward(qkv, out, lse)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        qkv, out, lse = ctx.saved_tensors
-        g = _chk(g, 'grad')
-        D = qkv.shape[1] // 3
-        dqkv = torch.empty_like(qkv)
-        _attn_long_bwd(g, qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], out, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
-                       ctx.heads, ctx.causal, ctx.drop)
-        return dqkv, None, None, None
+    probabilities: the backward recomputes them.""")
+_PackedAttentionLong = _qkv_function(
+    '_PackedAttentionLong', _ATTN_LONG, True,
+    "_AttentionLong on the channel thirds q | k | v of one qkv [B, 3D, T]; the gradient is one [B, 3D, T] tensor.")
 
 
 def attention_long(q, k, v, heads, causal, drop=None):
     """cross_attention's function, arguments and dropout site (name, shape (B*heads, Tq, Tk), indexing, generator decisions) at
     any lengths and head dimensions up to 64, by an online softmax over 64-key tiles on the fp32 matrix cores: no
     [B*heads, Tq, Tk] tensor is written in either pass (csrc/attn_long.hip)."""
-    return _AttentionLong.apply(q, k, v, heads, causal,
-                                _make_drop(drop, (q.shape[0] * heads, q.shape[2], k.shape[2]), q.device))
+    return _AttentionLong.apply(q, k, v, heads, causal, _make_drop(drop, _probs_shape(heads, q, k), q.device))
 
 
 def packed_attention_long(qkv, heads, causal, drop=None):
     """attention_long on qkv [B, 3D, T] (q | k | v along channels, an in_proj's output)."""
-    B, _, T = qkv.shape
-    return _PackedAttentionLong.apply(qkv, heads, causal, _make_drop(drop, (B * heads, T, T), qkv.device))
+    return _PackedAttentionLong.apply(qkv, heads, causal, _probs_drop(qkv, heads, drop))
 
 
 def _xattn_serves(dh, Tq, Tk):
