@@ -24,6 +24,10 @@
 //
 // One thread writes 4 consecutive x of one row: three float4 image stores, one float4 depth store, one 4-byte label store.
 // Every load is unconditional on an address clamped into the stored sample.
+//
+// Two entries share the per-pixel code: dynmm_rgbd_aug over a dense [S, H0, W0] store (NYUv2: one size per split) and
+// dynmm_rgbd_aug_ragged over flat stores with a per-image {offset, H0, W0} table (SUNRGB-D: four cameras, four sizes, mixed
+// within a batch; 64-bit offsets, a split is about 2e9 pixels).
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -153,44 +157,42 @@ __device__ __forceinline__ AugParams load_params(const int* __restrict__ params,
     return P;
 }
 
-__global__ void __launch_bounds__(256) rgbd_aug_kernel(
-    const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth, const unsigned char* __restrict__ label,
-    int S, int H0, int W0, const int* __restrict__ params, const float* __restrict__ hsv, int N, int H, int W,
-    float depth_mean, float depth_std, int raw_depth, float* __restrict__ image, float* __restrict__ depth_out,
-    unsigned char* __restrict__ label_out, unsigned char* __restrict__ down8, unsigned char* __restrict__ down16,
-    unsigned char* __restrict__ down32, int main_blocks) {
-    const size_t plane0 = (size_t)H0 * W0;
-    if ((int)blockIdx.x >= main_blocks) {
-        // label pyramid: one thread per pixel of label_down[8] / [16] / [32]
-        int t = ((int)blockIdx.x - main_blocks) * 256 + (int)threadIdx.x;
-        unsigned char* dst = nullptr;
-        int r = 8;
-        for (int k = 0; k < 3; ++k, r *= 2) {
-            const int cnt = N * (H / r) * (W / r);
-            if (t < cnt) {
-                dst = k == 0 ? down8 : (k == 1 ? down16 : down32);
-                break;
-            }
-            t -= cnt;
+// one pixel of the label pyramid: element t of the concatenated label_down[8] / [16] / [32] of the batch, from the stored
+// label map `lab` (H0 x W0) of sample n = element / (Hd * Wd); `pick` maps n to that sample's parameters and label map
+template <typename Pick>
+__device__ __forceinline__ void aug_pyramid_pixel(int t, int N, int H, int W, unsigned char* __restrict__ down8,
+                                                  unsigned char* __restrict__ down16, unsigned char* __restrict__ down32,
+                                                  Pick pick) {
+    unsigned char* dst = nullptr;
+    int r = 8;
+    for (int k = 0; k < 3; ++k, r *= 2) {
+        const int cnt = N * (H / r) * (W / r);
+        if (t < cnt) {
+            dst = k == 0 ? down8 : (k == 1 ? down16 : down32);
+            break;
         }
-        if (dst == nullptr) return;
-        const int Hd = H / r, Wd = W / r;
-        const int n = t / (Hd * Wd), rem = t % (Hd * Wd), dy = rem / Wd, dx = rem % Wd;
-        const AugParams P = load_params(params, n, S);
-        const int ya = nn_index(dy, H, Hd), xa = nn_index(dx, W, Wd);
-        int sy, sx;
-        nearest_src(P, H0, W0, H, W, ya, P.flip ? W - 1 - xa : xa, sy, sx);
-        dst[t] = label[P.src * plane0 + (size_t)sy * W0 + sx];
-        return;
+        t -= cnt;
     }
-    const int W4 = W >> 2;
-    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    if (q >= N * H * W4) return;
-    const int n = q / (H * W4), rem = q % (H * W4), y = rem / W4, x0 = (rem % W4) * 4;
-    const AugParams P = load_params(params, n, S);
-    const unsigned char* img = rgb + P.src * plane0 * 3;
-    const unsigned short* dep = depth + P.src * plane0;
-    const unsigned char* lab = label + P.src * plane0;
+    if (dst == nullptr) return;
+    const int Hd = H / r, Wd = W / r;
+    const int n = t / (Hd * Wd), rem = t % (Hd * Wd), dy = rem / Wd, dx = rem % Wd;
+    AugParams P;
+    const unsigned char* lab;
+    int H0, W0;
+    pick(n, P, lab, H0, W0);
+    const int ya = nn_index(dy, H, Hd), xa = nn_index(dx, W, Wd);
+    int sy, sx;
+    nearest_src(P, H0, W0, H, W, ya, P.flip ? W - 1 - xa : xa, sy, sx);
+    dst[t] = lab[(size_t)sy * W0 + sx];
+}
+
+// 4 consecutive x of row y of output sample n from one stored sample (img / dep / lab, H0 x W0): three float4 image stores,
+// one float4 depth store, one 4-byte label store
+__device__ __forceinline__ void aug_quad(const unsigned char* __restrict__ img, const unsigned short* __restrict__ dep,
+                                         const unsigned char* __restrict__ lab, int H0, int W0, const AugParams& P,
+                                         const float* __restrict__ hsv, int n, int y, int x0, int H, int W, float depth_mean,
+                                         float depth_std, int raw_depth, float* __restrict__ image,
+                                         float* __restrict__ depth_out, unsigned char* __restrict__ label_out) {
     float hf = 1.f, sf = 1.f, vf = 0.f;
     if (hsv) hf = hsv[4 * n], sf = hsv[4 * n + 1], vf = hsv[4 * n + 2];
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
@@ -242,6 +244,80 @@ __global__ void __launch_bounds__(256) rgbd_aug_kernel(
     *reinterpret_cast<uchar4*>(label_out + (size_t)n * plane + o) = make_uchar4(lv[0], lv[1], lv[2], lv[3]);
 }
 
+// 5 waves per SIMD = at most 96 VGPRs, what this kernel has always fitted in without scratch (through the shared functions
+// the allocator otherwise lands on 97, one wave less)
+__global__ void __launch_bounds__(256, 5) rgbd_aug_kernel(
+    const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth, const unsigned char* __restrict__ label,
+    int S, int H0, int W0, const int* __restrict__ params, const float* __restrict__ hsv, int N, int H, int W,
+    float depth_mean, float depth_std, int raw_depth, float* __restrict__ image, float* __restrict__ depth_out,
+    unsigned char* __restrict__ label_out, unsigned char* __restrict__ down8, unsigned char* __restrict__ down16,
+    unsigned char* __restrict__ down32, int main_blocks) {
+    const size_t plane0 = (size_t)H0 * W0;
+    if ((int)blockIdx.x >= main_blocks) {
+        // label pyramid: one thread per pixel of label_down[8] / [16] / [32]
+        aug_pyramid_pixel(((int)blockIdx.x - main_blocks) * 256 + (int)threadIdx.x, N, H, W, down8, down16, down32,
+                          [&](int n, AugParams& P, const unsigned char*& lab, int& h0, int& w0) {
+                              P = load_params(params, n, S);
+                              lab = label + P.src * plane0, h0 = H0, w0 = W0;
+                          });
+        return;
+    }
+    const int W4 = W >> 2;
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (q >= N * H * W4) return;
+    const int n = q / (H * W4), rem = q % (H * W4), y = rem / W4, x0 = (rem % W4) * 4;
+    const AugParams P = load_params(params, n, S);
+    aug_quad(rgb + P.src * plane0 * 3, depth + P.src * plane0, label + P.src * plane0, H0, W0, P, hsv, n, y, x0, H, W,
+             depth_mean, depth_std, raw_depth, image, depth_out, label_out);
+}
+
+// One stored image of a ragged store (flat rgb / depth / label arrays of `total` pixels): geom row {pixel offset, H0, W0, 0}
+// (int64 [S, 4]), read with two 16-byte loads.  The size is clamped into [1, 65535] (1 x 1 when it exceeds the store) and the
+// image into [0, total), so every address derived from it stays inside the stores whatever the table holds.
+struct RaggedImage {
+    long long off;
+    int H0, W0;
+};
+
+__device__ __forceinline__ RaggedImage load_geom(const long long* __restrict__ geom, int src, long long total) {
+    const longlong2 a = reinterpret_cast<const longlong2*>(geom)[2 * (size_t)src];
+    const longlong2 b = reinterpret_cast<const longlong2*>(geom)[2 * (size_t)src + 1];
+    long long h0 = a.y < 1 ? 1 : (a.y > 65535 ? 65535 : a.y), w0 = b.x < 1 ? 1 : (b.x > 65535 ? 65535 : b.x);
+    if (h0 * w0 > total) h0 = w0 = 1;
+    RaggedImage g;
+    g.H0 = (int)h0, g.W0 = (int)w0;
+    const long long last = total - h0 * w0;
+    g.off = a.x < 0 ? 0 : (a.x > last ? last : a.x);
+    return g;
+}
+
+// 101 VGPRs, 4 waves per SIMD, no scratch: the 64-bit offset and the per-lane H0 / W0 cost five registers over the uniform
+// kernel, and capping it at 96 spills four of them
+__global__ void __launch_bounds__(256) rgbd_aug_ragged_kernel(
+    const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth, const unsigned char* __restrict__ label,
+    const long long* __restrict__ geom, long long total, int S, const int* __restrict__ params, const float* __restrict__ hsv,
+    int N, int H, int W, float depth_mean, float depth_std, int raw_depth, float* __restrict__ image,
+    float* __restrict__ depth_out, unsigned char* __restrict__ label_out, unsigned char* __restrict__ down8,
+    unsigned char* __restrict__ down16, unsigned char* __restrict__ down32, int main_blocks) {
+    if ((int)blockIdx.x >= main_blocks) {
+        aug_pyramid_pixel(((int)blockIdx.x - main_blocks) * 256 + (int)threadIdx.x, N, H, W, down8, down16, down32,
+                          [&](int n, AugParams& P, const unsigned char*& lab, int& h0, int& w0) {
+                              P = load_params(params, n, S);
+                              const RaggedImage g = load_geom(geom, P.src, total);
+                              lab = label + g.off, h0 = g.H0, w0 = g.W0;
+                          });
+        return;
+    }
+    const int W4 = W >> 2;
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (q >= N * H * W4) return;
+    const int n = q / (H * W4), rem = q % (H * W4), y = rem / W4, x0 = (rem % W4) * 4;
+    const AugParams P = load_params(params, n, S);
+    const RaggedImage g = load_geom(geom, P.src, total);
+    aug_quad(rgb + g.off * 3, depth + g.off, label + g.off, g.H0, g.W0, P, hsv, n, y, x0, H, W, depth_mean, depth_std,
+             raw_depth, image, depth_out, label_out);
+}
+
 }  // namespace dynmm
 
 using namespace dynmm;
@@ -268,6 +344,33 @@ extern "C" int dynmm_rgbd_aug(const unsigned char* rgb, const unsigned short* de
     hipLaunchKernelGGL(rgbd_aug_kernel, dim3(main_blocks + down_blocks), dim3(256), 0, (hipStream_t)stream, rgb, depth, label,
                        S, H0, W0, params, hsv, N, H, W, depth_mean, depth_std, raw_depth, image, depth_out, label_out, down8,
                        down16, down32, main_blocks);
+    DYNMM_LAUNCH_CHECK();
+    return DYNMM_OK;
+}
+
+extern "C" int dynmm_rgbd_aug_ragged(const unsigned char* rgb, const unsigned short* depth, const unsigned char* label,
+                                     const long long* geom, long long total, int S, const int* params, const float* hsv, int N,
+                                     int H, int W, float depth_mean, float depth_std, int raw_depth, float* image,
+                                     float* depth_out, unsigned char* label_out, unsigned char* down8, unsigned char* down16,
+                                     unsigned char* down32, void* stream) {
+    (void)hipGetLastError();
+    if (!rgb || !depth || !label || !geom || !params || !image || !depth_out || !label_out || total < 1 || S < 1 || N < 1 ||
+        H < 1 || W < 1)
+        return DYNMM_EINVAL;
+    if ((down8 || down16 || down32) && !(down8 && down16 && down32)) return DYNMM_EINVAL;
+    // as dynmm_rgbd_aug, plus the 16-byte loads of the geom rows
+    if (W % 4 != 0 || ((uintptr_t)image & 15u) || ((uintptr_t)depth_out & 15u) || ((uintptr_t)label_out & 3u) ||
+        ((uintptr_t)params & 15u) || ((uintptr_t)geom & 15u))
+        return DYNMM_EUNSUPPORTED;
+    const long long quads = (long long)N * H * (W / 4);
+    long long down = 0;
+    if (down8)
+        for (int r = 8; r <= 32; r *= 2) down += (long long)N * (H / r) * (W / r);
+    if (quads + down > (long long)INT32_MAX - 256) return DYNMM_EUNSUPPORTED;
+    const int main_blocks = (int)((quads + 255) / 256), down_blocks = (int)((down + 255) / 256);
+    hipLaunchKernelGGL(rgbd_aug_ragged_kernel, dim3(main_blocks + down_blocks), dim3(256), 0, (hipStream_t)stream, rgb, depth,
+                       label, geom, total, S, params, hsv, N, H, W, depth_mean, depth_std, raw_depth, image, depth_out,
+                       label_out, down8, down16, down32, main_blocks);
     DYNMM_LAUNCH_CHECK();
     return DYNMM_OK;
 }

@@ -768,13 +768,18 @@ def evaluate(model, batches, num_classes=40, hard=True, class_weight=None, shard
             dp.dist.all_reduce(acc4, group=group)
     if losses is not None:
         losses.update(zip(('sum_weighted', 'weight_sum', 'sum_unweighted', 'pixels'), acc4.tolist()))
+    return miou_of(cm), cm.cpu()
+
+
+def miou_of(cm):
+    """mIoU * 100 of an int64 confusion matrix"""
     cmd = cm.double()
     iou = cmd.diag() / (cmd.sum(1) + cmd.sum(0) - cmd.diag() + 1e-15)
-    return iou.mean().item() * 100.0, cm.cpu()
+    return iou.mean().item() * 100.0
 
 
 def validate(model, loaders_by_camera, class_weight, logs=None, split='test', soft_eval=False, dynamic=True,
-             weighted_pixel_sum=None, num_classes=40, shard=True, group=None):
+             weighted_pixel_sum=None, num_classes=40, shard=True, group=None, all_cameras=False):
     """FusionDynMM/train.py:368-551 `validate` on the HIP path: one confusion matrix per camera (all images of a camera
     share a resolution, :398-404), mIoU per camera under `mIoU_{split}_{camera}`, the class-weighted validation loss
     `loss_{split}` = sum_px w[t]*CE / weighted_pixel_sum (src/utils.py:53-74; `weighted_pixel_sum` = sum_c pixels_c*w_c
@@ -782,7 +787,9 @@ def validate(model, loaders_by_camera, class_weight, logs=None, split='test', so
     which is the same number whenever the loader's labels are the data set's) and `loss_{split}_unweighted`
     (:77-97), hard gates unless `soft_eval` (:384), gate statistics through start_weight / end_weight (:385-387, :512).
     `loaders_by_camera`: {camera: iterable of dicts with image / depth / label_orig / label}.  Returns (miou, logs)
-    with `miou[camera]` and the confusion matrices under logs['confusion_matrices'] (train.py pickles them, :521-525)."""
+    with `miou[camera]` and the confusion matrices under logs['confusion_matrices'] (train.py pickles them, :521-525).
+    `all_cameras`: with more than one camera, also `miou['all']` = `logs[f'mIoU_{split}']`, the mIoU of the SUM of the cameras'
+    confusion matrices (ESANet's train.py:499-514; FusionDynMM left it commented out); with one camera nothing is added."""
     import time
     t0 = time.time()
     logs = {} if logs is None else logs
@@ -803,6 +810,8 @@ def validate(model, loaders_by_camera, class_weight, logs=None, split='test', so
     logs[f'loss_{split}_unweighted'] = tot['sum_unweighted'] / tot['pixels'] if tot['pixels'] else float('nan')
     for camera in loaders_by_camera:
         logs[f'mIoU_{split}_{camera}'] = miou[camera]
+    if all_cameras and len(cms) > 1:
+        miou['all'] = logs[f'mIoU_{split}'] = miou_of(sum(cms.values()))
     logs['time_validation'] = time.time() - t0
     logs['confusion_matrices'] = cms
     return miou, logs

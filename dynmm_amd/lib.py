@@ -225,6 +225,7 @@ SIGNATURES = {
     'dynmm_attn_long_fwd': (c_i, [c_f] * 3 + [c_ll] * 3 + [c_f, c_f] + [c_i] * 6 + [_DP, c_f]),
     'dynmm_attn_long_bwd': (c_i, [c_f] * 4 + [c_ll] * 3 + [c_f] * 5 + [c_ll] * 3 + [c_i] * 6 + [_DP, c_f]),
     'dynmm_rgbd_aug': (c_i, [c_f, c_f, c_f] + [c_i] * 3 + [c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
+    'dynmm_rgbd_aug_ragged': (c_i, [c_f, c_f, c_f, c_f, c_ll, c_i, c_f, c_f] + [c_i] * 3 + [c_fl, c_fl, c_i] + [c_f] * 7),
 }
 
 ABI_VERSION = 5

@@ -2642,3 +2642,39 @@ def rgbd_aug(rgb, depth, label, params, H, W, depth_mean, depth_std, raw_depth=F
                                depth_out.data_ptr(), lab.data_ptr(), *((down[r].data_ptr() for r in (8, 16, 32)) if down
                                                                       else (None, None, None)), _stream()), 'rgbd_aug')
     return image, depth_out, lab, down
+
+
+def rgbd_aug_ragged(rgb, depth, label, geom, params, H, W, depth_mean, depth_std, raw_depth=False, hsv=None, label_down=True):
+    """rgbd_aug over a ragged store (dynmm_amd/data.py SUNRGBD: images of several sizes, mixed within a batch): rgb [T,3] uint8,
+    depth [T] 16-bit, label [T] uint8 hold the images' pixels back to back, geom [S,4] int64 on the device is per stored image
+    {pixel offset, H0, W0, 0}, and params[:, 0] indexes geom.  Everything else, and what is returned, is rgbd_aug's."""
+    lib = _lib()
+    for t, name, dt in ((rgb, 'rgb', torch.uint8), (depth, 'depth', torch.int16), (label, 'label', torch.uint8),
+                        (geom, 'geom', torch.int64), (params, 'params', torch.int32)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise L.DynmmHipError(f'rgbd_aug_ragged: {name} must be a contiguous {dt} tensor on a HIP device')
+    T = label.numel()
+    if label.dim() != 1 or tuple(depth.shape) != (T,) or tuple(rgb.shape) != (T, 3) or T < 1:
+        raise L.DynmmHipError(f'rgbd_aug_ragged: rgb {tuple(rgb.shape)}, depth {tuple(depth.shape)}, label '
+                              f'{tuple(label.shape)}: expected [T, 3], [T], [T]')
+    if geom.dim() != 2 or geom.shape[1] != 4 or geom.shape[0] < 1:
+        raise L.DynmmHipError(f'rgbd_aug_ragged: geom must be [S, 4], got {tuple(geom.shape)}')
+    N = params.shape[0]
+    if params.dim() != 2 or params.shape[1] != 8:
+        raise L.DynmmHipError(f'rgbd_aug_ragged: params must be [N, 8], got {tuple(params.shape)}')
+    if hsv is not None and (not hsv.is_cuda or hsv.dtype != torch.float32 or tuple(hsv.shape) != (N, 4)
+                            or not hsv.is_contiguous()):
+        raise L.DynmmHipError('rgbd_aug_ragged: hsv must be a contiguous float32 [N, 4] tensor on the device')
+    if W % 4 != 0:
+        raise L.DynmmHipError(f'rgbd_aug_ragged: width {W} must be a multiple of 4')
+    dev = rgb.device
+    image = torch.empty(N, 3, H, W, device=dev)
+    depth_out = torch.empty(N, 1, H, W, device=dev)
+    lab = torch.empty(N, H, W, device=dev, dtype=torch.uint8)
+    down = {r: torch.empty(N, H // r, W // r, device=dev, dtype=torch.uint8) for r in (8, 16, 32)} if label_down else None
+    L.check(lib.dynmm_rgbd_aug_ragged(rgb.data_ptr(), depth.data_ptr(), label.data_ptr(), geom.data_ptr(), T, geom.shape[0],
+                                      params.data_ptr(), _p(hsv), N, H, W, float(depth_mean), float(depth_std),
+                                      int(bool(raw_depth)), image.data_ptr(), depth_out.data_ptr(), lab.data_ptr(),
+                                      *((down[r].data_ptr() for r in (8, 16, 32)) if down else (None, None, None)), _stream()),
+            'rgbd_aug_ragged')
+    return image, depth_out, lab, down

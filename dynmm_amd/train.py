@@ -45,6 +45,15 @@ def save_ckpt(ckpt_dir, model, opt, epoch, best_miou=None, best_miou_epoch=None)
     return path
 
 
+def make_ckpt_dir(args, rank=0):
+    ckpt_dir = os.path.join(args.results_dir, args.dataset, time.strftime('checkpoints_%d_%m_%Y-%H_%M_%S'))
+    if rank == 0:
+        os.makedirs(ckpt_dir, exist_ok=True)
+        with open(os.path.join(ckpt_dir, 'args.json'), 'w') as f:
+            json.dump(vars(args), f, sort_keys=True, indent=4)
+    return ckpt_dir
+
+
 def train_main(argv=None):
     args = parse_args(argv)
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -56,12 +65,9 @@ def train_main(argv=None):
                                   'dynmm_amd.train.run(...) for real data (NYUv2 preparation is host-side code '
                                   'outside the hot path)')
     if args.dataset not in ('synthetic', 'nyuv2'):
-        raise NotImplementedError(f'--dataset {args.dataset}: only nyuv2 (and synthetic) have a reader on the HIP path')
-    ckpt_dir = os.path.join(args.results_dir, args.dataset, time.strftime('checkpoints_%d_%m_%Y-%H_%M_%S'))
-    if rank == 0:
-        os.makedirs(ckpt_dir, exist_ok=True)
-        with open(os.path.join(ckpt_dir, 'args.json'), 'w') as f:
-            json.dump(vars(args), f, sort_keys=True, indent=4)
+        raise NotImplementedError(f'--dataset {args.dataset}: only nyuv2 (and synthetic) have a reader on the HIP path here; '
+                                  'SUNRGB-D trains through python -m dynmm_amd.sunrgbd train')
+    ckpt_dir = make_ckpt_dir(args, rank)
     model, device = build_for_args(args, n_classes=40)
     if args.dataset == 'nyuv2':
         train, valid = prepare_data(args, device, rank, world, seed=args.data_seed)
@@ -76,11 +82,24 @@ def train_main(argv=None):
 CAMERA = 'kv1'        # NYUv2's only camera (src/datasets/nyuv2/nyuv2.py: CAMERAS); train.py:217 reports mIoU_test_kv1
 
 
+def n_classes_of(loader):
+    return getattr(loader, 'n_classes_without_void', 40)
+
+
+def loaders_by_camera(valid_loader):
+    """{camera: batches} as engine.validate takes it: a loader's own by_camera() (SUNRGB-D: four cameras), else the whole
+    loader under its single camera's name (NYUv2, synthetic: kv1)"""
+    if hasattr(valid_loader, 'by_camera'):
+        return valid_loader.by_camera()
+    cameras = getattr(valid_loader, 'cameras', None) or [CAMERA]
+    return {cameras[0]: valid_loader}
+
+
 def class_weights(args, train_loader, world=1):
     """--class_weighting over the WHOLE training set (train.py:100-103): each rank holds a shard of it, so the two label
     histograms are summed over ranks before the weights are formed — every replica then weighs its CE identically."""
     if args.class_weighting == 'None':
-        return np.ones(40)
+        return np.ones(n_classes_of(train_loader))
     if world > 1 and hasattr(train_loader, 'class_counts'):
         per, with_ = train_loader.class_counts()
         both = torch.from_numpy(np.stack([per, with_]))                 # float64 pixel counts: exact in a sum over ranks
@@ -144,12 +163,15 @@ def run(args, model, train_loader, valid_loader, ckpt_dir, rank=0, world=1):
         if epoch == start_epoch or epoch % args.eval_every == 0:        # train.py:207
             # validate (train.py:368-551): per-camera mIoU + weighted / unweighted validation loss; under data parallel
             # the validation batches are sharded over the ranks and the confusion matrix is all-reduced once
-            miou, row = engine.validate(model, {CAMERA: valid_loader}, cw, logs=row, split='test',
-                                        soft_eval=args.soft_eval, dynamic=args.dynamic)
+            by_camera = loaders_by_camera(valid_loader)
+            miou, row = engine.validate(model, by_camera, cw, logs=row, split='test', soft_eval=args.soft_eval,
+                                        dynamic=args.dynamic, num_classes=n_classes_of(train_loader), all_cameras=True)
             row.pop('confusion_matrices', None)
-            row['mIoU_test'] = miou[CAMERA]
-            if miou[CAMERA] > best_miou:
-                best_miou, best_epoch = miou[CAMERA], epoch
+            # the figure the best checkpoint goes by: all cameras together where there are several, else the only one
+            current = miou['all'] if 'all' in miou else miou[next(iter(by_camera))]
+            row['mIoU_test'] = current
+            if current > best_miou:
+                best_miou, best_epoch = current, epoch
                 if rank == 0:
                     # train.py:235 deep-copies the model here; a CPU snapshot of its state_dict is what gets saved
                     # (rank 0 only: it is the rank that writes checkpoints)

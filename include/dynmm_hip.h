@@ -893,6 +893,15 @@ int dynmm_rgbd_aug(const unsigned char* rgb, const unsigned short* depth, const 
                    const int* params, const float* hsv, int N, int H, int W, float depth_mean, float depth_std, int raw_depth,
                    float* image, float* depth_out, unsigned char* label_out, unsigned char* down8, unsigned char* down16,
                    unsigned char* down32, void* stream);
+/* The same outputs from a RAGGED store (SUNRGB-D: images of different sizes in one batch): rgb [total,3] uint8, depth [total]
+ * 16-bit, label [total] uint8 hold the images back to back; geom [S,4] int64 on the device gives per stored image {pixel
+ * offset, H0, W0, 0} and is indexed by params[:,0] (clamped into [0, S)).  Offsets are 64-bit.  The kernel clamps each row of
+ * geom into the `total` pixels of the stores.  Same refusals as dynmm_rgbd_aug; geom non-NULL and 16-byte aligned. */
+int dynmm_rgbd_aug_ragged(const unsigned char* rgb, const unsigned short* depth, const unsigned char* label,
+                          const long long* geom, long long total, int S, const int* params, const float* hsv, int N, int H,
+                          int W, float depth_mean, float depth_std, int raw_depth, float* image, float* depth_out,
+                          unsigned char* label_out, unsigned char* down8, unsigned char* down16, unsigned char* down32,
+                          void* stream);
 
 #ifdef __cplusplus
 }
