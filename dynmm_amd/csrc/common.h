@@ -62,6 +62,14 @@ __device__ __forceinline__ T block_reduce_sum_256(T v, T* smem) {
     return r;
 }
 
+__device__ __forceinline__ float row16_sum(float v) {            // sum over the lane's row of 16 lanes, in every lane of it
+    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));      // quad_perm [1,0,3,2]
+    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));      // quad_perm [2,3,0,1]
+    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true));     // row_half_mirror
+    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, true));     // row_mirror
+    return v;
+}
+
 // r[0 .. N-1] = p[0 .. N-1] in the widest units N allows (the attention kernels' LDS rows: one address for every lane, a
 // broadcast); p: aligned to the widest unit used
 template <int N>

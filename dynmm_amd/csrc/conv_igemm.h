@@ -3,10 +3,34 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "mfma.h"
 
 namespace dynmm {
 
+// a compile-time int as a function argument (the ring kernels' lambdas take their buffer set / stage as one)
+template <int I>
+using ic = std::integral_constant<int, I>;
+
+// ---- host checks shared by the convolution entry points -----------------------------------------------------------------
+// every pointer (a null one included) is a multiple of A bytes, A a power of two
+template <int A, typename... P>
+static inline bool ptrs_aligned(const P*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & (uintptr_t)(A - 1)) == 0;
+}
+
+// the kernels form 32-bit BYTE offsets into their tensors: N * C * H * W floats must stay under 2^30 for either channel count
+static inline bool offsets_fit_32(int N, int Ci, int Co, int H, int W) {
+    return (double)N * (Ci > Co ? Ci : Co) * H * W < 1073741824.0;
+}
+
+// statistics slabs of an epilogue that adds per-channel sums with atomics: pixel tile p adds into slab p % slots, so that at
+// most 600 tiles meet on one address (thousands serialise: 4800 tiles on one address cost a C = 64 launch 18 %), 1 .. 8 slabs
+static inline int stat_slots(int tiles) {
+    const int s = tiles / 600;
+    return s < 1 ? 1 : (s > 8 ? 8 : s);
+}
 
 struct IgemmArgs {
     const float* x;        // gemm input  [N, Ci, H, W]  (first c_in_split channels)

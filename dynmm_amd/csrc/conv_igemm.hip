@@ -19,6 +19,7 @@
 #include "common.h"
 #include "conv_igemm.h"
 #include "conv_small.h"
+#include "pack_desc.h"
 #include "vec.h"
 
 namespace dynmm {
@@ -497,7 +498,7 @@ namespace dynmm {
 #endif
 
 // rows per filter tap of a packed weight / K-steps of the fast path (see pack_weight_kernel)
-static inline int round_k(int c) { return (c >= 8 && c % 16 != 0) ? ((c + 15) & ~15) : c; }
+__host__ __device__ static inline int round_k(int c) { return (c >= 8 && c % 16 != 0) ? ((c + 15) & ~15) : c; }
 
 template <bool DGRAD>
 static int launch_igemm(IgemmArgs& a, hipStream_t st) {
@@ -1269,11 +1270,9 @@ void launch_reduce_slabs(const float* slabs, float* out, int n, int nslabs, hipS
 // wf[(tap*CiR+ci)*CoP + co], wd[(tap*CoR+co)*CiP + ci]: CoP / CiP = row length rounded up to 4 floats, CiR / CoR =
 // rows per tap (round_k: rounded up to 16 for 8 <= C, C % 16 != 0, so those convs run the one-tap-per-K-step fast
 // path with a few zero rows instead of the element-wise generic loader).  Every padding element is written as 0.
-__global__ void __launch_bounds__(256) pack_weight_kernel(const float* __restrict__ w,
-                                                          float* __restrict__ wf,
-                                                          float* __restrict__ wd,
-                                                          int Co, int Ci, int KHKW, int CoP, int CiP, int CiR, int CoR) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+// Element i of the two layouts laid end to end (wf, wd: either may be null).
+__device__ __forceinline__ void pack_weight_one(const float* __restrict__ w, float* __restrict__ wf, float* __restrict__ wd,
+                                                int Co, int Ci, int KHKW, int CoP, int CiP, int CiR, int CoR, int i) {
     const int nf = wf ? KHKW * CiR * CoP : 0;
     const int nd = wd ? KHKW * CoR * CiP : 0;
     if (i < nf) {
@@ -1286,6 +1285,13 @@ __global__ void __launch_bounds__(256) pack_weight_kernel(const float* __restric
         const int co = k % CoR, tap = k / CoR;
         wd[j] = (co < Co && ci < Ci) ? w[((size_t)co * Ci + ci) * KHKW + tap] : 0.f;
     }
+}
+
+__global__ void __launch_bounds__(256) pack_weight_kernel(const float* __restrict__ w,
+                                                          float* __restrict__ wf,
+                                                          float* __restrict__ wd,
+                                                          int Co, int Ci, int KHKW, int CoP, int CiP, int CiR, int CoR) {
+    pack_weight_one(w, wf, wd, Co, Ci, KHKW, CoP, CiP, CiR, CoR, blockIdx.x * 256 + threadIdx.x);
 }
 
 // All conv weights of a model in ONE launch (engine.TrainStep: 186 pack launches per step otherwise).  desc[d] =
@@ -1314,33 +1320,14 @@ __global__ void __launch_bounds__(256) pack_weight_multi_kernel(const float* __r
                                                                 float* __restrict__ dst_base,
                                                                 const PackDesc* __restrict__ desc, int ndesc) {
     __shared__ float tile[32][32 * kPackTapsMax + 1];
-    int lo = 0, hi = ndesc - 1;                    // last descriptor whose first workgroup is <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (desc[mid].blk0 <= (int)blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const PackDesc d = desc[lo];
-    const int CoP = (d.Co + 3) & ~3, CiP = (d.Ci + 3) & ~3;
-    const int CiR = (d.Ci >= 8 && d.Ci % 16 != 0) ? ((d.Ci + 15) & ~15) : d.Ci;
-    const int CoR = (d.Co >= 8 && d.Co % 16 != 0) ? ((d.Co + 15) & ~15) : d.Co;
+    const PackDesc d = pack_desc_find(desc, ndesc);
+    const int CoP = (d.Co + 3) & ~3, CiP = (d.Ci + 3) & ~3, CiR = round_k(d.Ci), CoR = round_k(d.Co);
     const float* __restrict__ w = src_base + d.src;
     const int KK = d.KHKW;
     const int blk = (int)blockIdx.x - d.blk0;
     if (KK > kPackTapsMax) {                       // element-wise path (stems, gate convs)
-        const int i = blk * 256 + threadIdx.x;
-        const int nf = KK * CiR * CoP;
-        const int nd = d.dstd >= 0 ? KK * CoR * CiP : 0;
-        if (i < nf) {
-            const int co = i % CoP, k = i / CoP;
-            const int ci = k % CiR, tap = k / CiR;
-            dst_base[d.dstf + i] = (co < d.Co && ci < d.Ci) ? w[((size_t)co * d.Ci + ci) * KK + tap] : 0.f;
-        } else if (i - nf < nd) {
-            const int j = i - nf;
-            const int ci = j % CiP, k = j / CiP;
-            const int co = k % CoR, tap = k / CoR;
-            dst_base[d.dstd + j] = (co < d.Co && ci < d.Ci) ? w[((size_t)co * d.Ci + ci) * KK + tap] : 0.f;
-        }
+        pack_weight_one(w, dst_base + d.dstf, d.dstd >= 0 ? dst_base + d.dstd : nullptr, d.Co, d.Ci, KK, CoP, CiP, CiR, CoR,
+                        blk * 256 + threadIdx.x);
         return;
     }
     const bool dg = d.dstd >= 0;

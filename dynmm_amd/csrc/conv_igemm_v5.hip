@@ -28,9 +28,6 @@
 
 namespace dynmm {
 
-template <int I>
-using ic = std::integral_constant<int, I>;
-
 template <int TCO, int TPIX, int WCO, int WPIX, int KW, bool DGRAD, int SA, int SB>
 __global__ void __launch_bounds__(256, 3) conv_igemm_v5_kernel(const IgemmArgs a) {
     // ring depths: SA weight stages; SB activation stages (KW = 3: two stages of three K-steps each; KW = 1: one per step)

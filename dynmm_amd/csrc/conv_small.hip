@@ -165,14 +165,6 @@ struct Co8WgradArgs {
     int N, Ci, H, W, Co, Ho, Wo, c_split, NI, G;
 };
 
-__device__ __forceinline__ float row16_sum(float v) {            // sum over the lane's row of 16 lanes, in every lane of it
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));      // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));      // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true));     // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, true));     // row_mirror
-    return v;
-}
-
 template <int KS, int S>
 __global__ void __launch_bounds__(256, 1) conv_co8_wgrad_kernel(const Co8WgradArgs a) {
     constexpr int PR = 16;                             // output rows per pass (4 waves x 4 lane rows)

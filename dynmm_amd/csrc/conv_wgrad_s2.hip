@@ -25,9 +25,6 @@
 
 namespace dynmm {
 
-template <int I>
-using ic2 = std::integral_constant<int, I>;
-
 template <int MCO, bool VT, int OCC>
 __global__ void __launch_bounds__(256, OCC) conv_wgrad_s2_kernel(const WgradArgs a_in, const WgradGroup grp) {
 #ifndef DYNMM_S2_NST
@@ -284,7 +281,7 @@ __global__ void __launch_bounds__(256, OCC) conv_wgrad_s2_kernel(const WgradArgs
     if (nsteps > 0) {
         if (NST == 3 && nsteps >= 3) wait_vm<2 * J>(); else if (nsteps >= 2) wait_vm<J>(); else wait_vm<0>();
         __syncthreads();
-        read_frags(ic2<0>{}, 0);
+        read_frags(ic<0>{}, 0);
     }
     int slot = 0;                                   // slot of stage s
     // one step: the set of step s is in registers.  This wave's requests for stage s + 1 have landed; after the barrier so
@@ -296,14 +293,14 @@ __global__ void __launch_bounds__(256, OCC) conv_wgrad_s2_kernel(const WgradArgs
             if (NST == 3 && s + 2 < nsteps) wait_vm<J>(); else wait_vm<0>();
             __syncthreads();
             if (s + NST < nsteps) issue(slot);
-            read_frags(ic2<1 - S>{}, next);
+            read_frags(ic<1 - S>{}, next);
         }
         mfmas(SET);
         slot = next;
     };
     for (int s = 0; s < nsteps; s += 2) {
-        step(ic2<0>{}, s);
-        if (s + 1 < nsteps) step(ic2<1>{}, s + 1);
+        step(ic<0>{}, s);
+        if (s + 1 < nsteps) step(ic<1>{}, s + 1);
     }
 
     if (do_bias && t < TCO) a.out_bias[(size_t)split * a.Co + co0 + t] = bsum;

@@ -31,9 +31,6 @@
 
 namespace dynmm {
 
-template <int I>
-using ic = std::integral_constant<int, I>;
-
 // WINO (horizontal taps): the three taps of a pixel PAIR come from FOUR contractions instead of six — the weight-gradient
 // form of the 1-D Winograd algorithm the input-gradient kernels use (conv_wino.hip): with e0, e1 the pair's dY values and
 // d0..d3 the four X values under them,

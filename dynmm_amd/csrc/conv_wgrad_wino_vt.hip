@@ -54,9 +54,6 @@
 
 namespace dynmm {
 
-template <int I>
-using icv = std::integral_constant<int, I>;
-
 template <int MCO>
 __global__ void __launch_bounds__(256, 2) conv_wgrad_wino_vt_kernel(const WgradArgs a_in, const WgradGroup grp) {
     WgradArgs a = a_in;
@@ -312,16 +309,16 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_wino_vt_kernel(const WgradA
             else wait_vm<J>();
         }
         __syncthreads();
-        read_frags(icv<0>{}, 0);
+        read_frags(ic<0>{}, 0);
         for (int s = 0; s < n_stages; ++s) {
             // half-step 0 of stage s is in set 0
-            read_frags(icv<1>{}, 1);
-            mfmas(icv<0>{});
+            read_frags(ic<1>{}, 1);
+            mfmas(ic<0>{});
             if (s + 1 < n_stages) {
                 advance();
-                read_frags(icv<0>{}, 0);
+                read_frags(ic<0>{}, 0);
             }
-            mfmas(icv<1>{});
+            mfmas(ic<1>{});
         }
     }
 

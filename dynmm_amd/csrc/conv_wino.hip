@@ -33,6 +33,7 @@
 
 #include "common.h"
 #include "conv_igemm.h"
+#include "pack_desc.h"
 
 namespace dynmm {
 
@@ -552,12 +553,12 @@ __global__ void __launch_bounds__(256, MCO == 1 ? ((VERT && !DGRAD) ? 4 : 3) : 2
 }
 
 // Filter transforms.  w [Co][Ci][3 taps] -> ut [K][C][4] with (K, C) = (Ci, Co) for the forward operand and (Co, Ci)
-// for the input gradient's (whose taps run the other way along the Winograd axis: g0 <-> g2).
-__global__ void __launch_bounds__(256) wino_pack_kernel(const float* __restrict__ w, float4* __restrict__ ut,
-                                                        const float* __restrict__ scale, int Co, int Ci, int dgrad) {
+// for the input gradient's (whose taps run the other way along the Winograd axis: g0 <-> g2).  Element o = k * Cc + c of one
+// operand; scale: per-tensor packs only.
+__device__ __forceinline__ void wino_pack_one(const float* __restrict__ w, float4* __restrict__ ut, const float* __restrict__ scale,
+                                              int Co, int Ci, int dgrad, size_t o) {
     const int K = dgrad ? Co : Ci, Cr = dgrad ? Ci : Co, Cc = (Cr + 63) & ~63;      // rows padded to the 64-row tile (zeros)
     const size_t total = (size_t)K * Cc;
-    const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (o >= total) return;
     const int c = (int)(o % Cc);
     const int k = (int)(o / Cc);
@@ -580,42 +581,17 @@ __global__ void __launch_bounds__(256) wino_pack_kernel(const float* __restrict_
     ut[o] = make_float4(g0, (g0 + g1 + g2) * 0.5f, (g0 - g1 + g2) * 0.5f, g2);
 }
 
-// Many filters in one launch (ops.PackedWeights: once per training step).  desc[d] = {src, dst: float offsets from the
-// two bases; Co | Ci << 32; KH | KW << 8 | dgrad << 16 | first workgroup << 32} (KH, KW: 3x1 or 1x3 — three taps either way).
-struct WinoPackDesc {
-    long long src, dst;
-    int Co, Ci, kk, blk0;
-};
+__global__ void __launch_bounds__(256) wino_pack_kernel(const float* __restrict__ w, float4* __restrict__ ut,
+                                                        const float* __restrict__ scale, int Co, int Ci, int dgrad) {
+    wino_pack_one(w, ut, scale, Co, Ci, dgrad, (size_t)blockIdx.x * 256 + threadIdx.x);
+}
 
+// Many filters in one launch (ops.PackedWeights: once per training step; KH, KW: 3x1 or 1x3 — three taps either way).
 __global__ void __launch_bounds__(256) wino_pack_multi_kernel(const float* __restrict__ src_base, float* __restrict__ dst_base,
                                                               const WinoPackDesc* __restrict__ desc, int ndesc) {
-    int lo = 0, hi = ndesc - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (desc[mid].blk0 <= (int)blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const WinoPackDesc d = desc[lo];
-    const int dgrad = (d.kk >> 16) & 3;
-    const int K = dgrad ? d.Co : d.Ci, Cr = dgrad ? d.Ci : d.Co, Cc = (Cr + 63) & ~63;
-    const size_t total = (size_t)K * Cc;
-    const size_t o = (size_t)((int)blockIdx.x - d.blk0) * 256 + threadIdx.x;
-    if (o >= total) return;
-    const int c = (int)(o % Cc);
-    const int k = (int)(o / Cc);
-    if (c >= Cr) {
-        reinterpret_cast<float4*>(dst_base + d.dst)[o] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    const int co = dgrad ? k : c, ci = dgrad ? c : k;
-    const float* g = src_base + d.src + ((size_t)co * d.Ci + ci) * 3;
-    float g0 = g[0], g1 = g[1], g2 = g[2];
-    if (dgrad == 2) {
-        reinterpret_cast<float4*>(dst_base + d.dst)[o] = make_float4(g1, g2, g0, 0.f);
-        return;
-    }
-    if (dgrad) { const float tmp = g0; g0 = g2; g2 = tmp; }
-    reinterpret_cast<float4*>(dst_base + d.dst)[o] = make_float4(g0, (g0 + g1 + g2) * 0.5f, (g0 - g1 + g2) * 0.5f, g2);
+    const WinoPackDesc d = pack_desc_find(desc, ndesc);
+    wino_pack_one(src_base + d.src, reinterpret_cast<float4*>(dst_base + d.dst), nullptr, d.Co, d.Ci, (d.kk >> 16) & 3,
+                  (size_t)((int)blockIdx.x - d.blk0) * 256 + threadIdx.x);
 }
 
 // rows = output channels of the GEMM (a multiple of the 64-row tile), red = its reduction channels (8 per stage, >= 3 stages):
@@ -631,7 +607,7 @@ static bool wino_geom_ok(const dynmm_conv_geom* g, bool dgrad) {
     const int rows = dgrad ? g->Ci : g->Co, red = dgrad ? g->Co : g->Ci;
     if ((dgrad ? rows % 64 != 0 : (rows % 8 != 0 || rows < 24)) || red % 8 != 0 || red < 24) return false;
     if ((long long)g->N * g->H * g->W < 256) return false;
-    if ((double)g->N * (g->Ci > g->Co ? g->Ci : g->Co) * g->H * g->W >= 1073741824.0) return false;   // 32-bit byte offsets
+    if (!offsets_fit_32(g->N, g->Ci, g->Co, g->H, g->W)) return false;
     return true;
 }
 
@@ -647,7 +623,7 @@ static bool wino_s2_geom_ok(const dynmm_conv_geom* g) {
     if (g->W % 4 != 0 || g->Wo % 4 != 0 || g->Wo < 4 || g->Ho < 1) return false;
     if (g->Ci % 64 != 0 || g->Co % 8 != 0 || g->Co < 24) return false;
     if ((long long)g->N * g->Ho * g->Wo < 256) return false;
-    if ((double)g->N * (g->Ci > g->Co ? g->Ci : g->Co) * g->H * g->W >= 1073741824.0) return false;
+    if (!offsets_fit_32(g->N, g->Ci, g->Co, g->H, g->W)) return false;
     return true;
 }
 
@@ -695,6 +671,18 @@ static int launch_wino(WinoArgs& a, bool vert, bool dgrad, hipStream_t st, bool 
     return DYNMM_OK;
 }
 
+// The input gradient's arguments from (dy, ut, g): dy is the kernel's input and the roles of the channel counts swap; the
+// callers add their epilogue operands.
+static WinoArgs wino_dgrad_args(const float* dy, const float* ut, const dynmm_conv_geom* g) {
+    WinoArgs a{};
+    a.x = dy; a.ut = ut;
+    a.N = g->N; a.Ci = g->Co; a.Co = g->Ci; a.H = g->H; a.W = g->W;
+    a.CoS = (a.Co + 63) & ~63;
+    a.act = DYNMM_ACT_NONE;
+    a.Hin = g->Ho; a.Win = g->Wo;                                             // (stride 2: dy is half as high / wide as dx)
+    return a;
+}
+
 }  // namespace dynmm
 
 using namespace dynmm;
@@ -717,7 +705,7 @@ extern "C" int dynmm_wino_pack(const float* w, float* ut, const float* scale, in
     (void)hipGetLastError();
     if (!w || !ut || Co <= 0 || Ci <= 0 || (scale && dgrad) || dgrad < 0 || dgrad > 2) return DYNMM_EINVAL;
     if (!((KH == 1 && KW == 3) || (KH == 3 && KW == 1))) return DYNMM_EUNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(ut) & 15u) return DYNMM_EINVAL;
+    if (!ptrs_aligned<16>(ut)) return DYNMM_EINVAL;
     const size_t total = dynmm_wino_packed_floats(Co, Ci, KH, KW) / 4;
     hipLaunchKernelGGL(wino_pack_kernel, dim3((unsigned)ceil_div_sz(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
                        reinterpret_cast<float4*>(ut), scale, Co, Ci, dgrad);
@@ -731,14 +719,7 @@ extern "C" int dynmm_wino_pack_multi_blocks(int Co, int Ci, int KH, int KW) {
 
 extern "C" int dynmm_wino_pack_multi(const float* src_base, float* dst_base, const void* desc, int ndesc, int total_blocks,
                                      void* stream) {
-    (void)hipGetLastError();
-    if (!src_base || !dst_base || !desc || ndesc <= 0 || total_blocks <= 0) return DYNMM_EINVAL;
-    if (reinterpret_cast<uintptr_t>(dst_base) & 15u) return DYNMM_EINVAL;
-    static_assert(sizeof(WinoPackDesc) == 32, "descriptor layout is part of the ABI (4 x int64 words)");
-    hipLaunchKernelGGL(wino_pack_multi_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, src_base, dst_base,
-                       (const WinoPackDesc*)desc, ndesc);
-    DYNMM_LAUNCH_CHECK();
-    return DYNMM_OK;
+    return launch_wino_pack_multi(wino_pack_multi_kernel, src_base, dst_base, desc, ndesc, total_blocks, stream);
 }
 
 extern "C" int dynmm_conv2d_wino_fwd(const float* x, const float* ut, const float* bias, const float* residual, float* y,
@@ -747,8 +728,7 @@ extern "C" int dynmm_conv2d_wino_fwd(const float* x, const float* ut, const floa
     if (!x || !ut || !y || !g) return DYNMM_EINVAL;
     if (!act_is_known(act)) return DYNMM_EINVAL;
     if (!wino_geom_ok(g, false)) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual)) & 7u) return DYNMM_EUNSUPPORTED;
+    if (!ptrs_aligned<16>(x, ut) || !ptrs_aligned<8>(y, residual)) return DYNMM_EUNSUPPORTED;
     WinoArgs a{};
     a.x = x; a.ut = ut; a.shift = bias; a.residual = residual; a.mask = nullptr; a.y = y;
     a.N = g->N; a.Ci = g->Ci; a.Co = g->Co; a.H = g->H; a.W = g->W;
@@ -763,11 +743,8 @@ extern "C" int dynmm_conv2d_wino_dgrad_bnred_supported(const dynmm_conv_geom* g)
 }
 
 extern "C" int dynmm_conv2d_wino_dgrad_bnred_slots(const dynmm_conv_geom* g) {
-    // thousands of pixel tiles adding to one address serialise (measured on the forward's statistics: 4800 tiles on one
-    // address cost a C = 64 launch 18 %): pixel tile p adds into slab p % slots, <= 600 tiles per address up to 8 slabs
     if (!dynmm_conv2d_wino_dgrad_bnred_supported(g)) return 0;
-    const int s = ceil_div(g->N * ((g->H + 1) / 2) * g->W, 64) / 600;
-    return s < 1 ? 1 : (s > 8 ? 8 : s);
+    return stat_slots(ceil_div(g->N * ((g->H + 1) / 2) * g->W, 64));
 }
 
 extern "C" int dynmm_conv2d_wino_dgrad_bnred(const float* dy, const float* ut, const float* bn_x, const float* bn_mean,
@@ -776,17 +753,11 @@ extern "C" int dynmm_conv2d_wino_dgrad_bnred(const float* dy, const float* ut, c
     (void)hipGetLastError();
     if (!dy || !ut || !bn_x || !bn_mean || !bn_invstd || !bn_gamma || !bn_beta || !sums || !dx || !g) return DYNMM_EINVAL;
     if (!dynmm_conv2d_wino_dgrad_bnred_supported(g)) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(bn_x) | reinterpret_cast<uintptr_t>(sums)) & 7u)
-        return DYNMM_EUNSUPPORTED;
-    WinoArgs a{};
-    a.x = dy; a.ut = ut; a.shift = nullptr; a.residual = nullptr; a.mask = bn_x; a.y = dx;
+    if (!ptrs_aligned<16>(dy, ut) || !ptrs_aligned<8>(dx, bn_x, sums)) return DYNMM_EUNSUPPORTED;
+    WinoArgs a = wino_dgrad_args(dy, ut, g);
+    a.mask = bn_x; a.y = dx;
     a.stats = sums; a.nslots = dynmm_conv2d_wino_dgrad_bnred_slots(g);
     a.bn_mean = bn_mean; a.bn_invstd = bn_invstd; a.bn_gamma = bn_gamma; a.bn_beta = bn_beta;
-    a.N = g->N; a.Ci = g->Co; a.Co = g->Ci; a.H = g->H; a.W = g->W;
-    a.CoS = (a.Co + 63) & ~63;
-    a.act = DYNMM_ACT_NONE;
-    a.Hin = g->Ho; a.Win = g->Wo;
     return launch_wino(a, true, true, (hipStream_t)stream);
 }
 
@@ -796,18 +767,11 @@ extern "C" int dynmm_conv2d_wino_dgrad_bnred2(const float* dy, const float* ut, 
     (void)hipGetLastError();
     if (!dy || !ut || !bn_x || !relu_bits || !bn_mean || !bn_invstd || !sums || !dx || !g) return DYNMM_EINVAL;
     if (!dynmm_conv2d_wino_dgrad_bnred_supported(g) || (g->H * g->W) % 4 != 0) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(bn_x) | reinterpret_cast<uintptr_t>(accum) |
-         reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(relu_bits)) & 7u)
-        return DYNMM_EUNSUPPORTED;
-    WinoArgs a{};
-    a.x = dy; a.ut = ut; a.shift = nullptr; a.residual = accum; a.mask = bn_x; a.y = dx;
+    if (!ptrs_aligned<16>(dy, ut) || !ptrs_aligned<8>(dx, bn_x, accum, sums, relu_bits)) return DYNMM_EUNSUPPORTED;
+    WinoArgs a = wino_dgrad_args(dy, ut, g);
+    a.residual = accum; a.mask = bn_x; a.y = dx;
     a.stats = sums; a.nslots = dynmm_conv2d_wino_dgrad_bnred_slots(g); a.bits = relu_bits;
     a.bn_mean = bn_mean; a.bn_invstd = bn_invstd; a.bn_gamma = bn_invstd; a.bn_beta = bn_invstd;      // (gamma / beta: BNRED == 1 only)
-    a.N = g->N; a.Ci = g->Co; a.Co = g->Ci; a.H = g->H; a.W = g->W;
-    a.CoS = (a.Co + 63) & ~63;
-    a.act = DYNMM_ACT_NONE;
-    a.Hin = g->Ho; a.Win = g->Wo;
     return launch_wino(a, true, true, (hipStream_t)stream);
 }
 
@@ -817,9 +781,7 @@ extern "C" int dynmm_conv2d_wino_fwd_stats_supported(const dynmm_conv_geom* g) {
 
 extern "C" int dynmm_conv2d_wino_fwd_stats_slots(const dynmm_conv_geom* g) {
     if (!dynmm_conv2d_wino_fwd_stats_supported(g)) return 0;
-    const int tiles = ceil_div(g->N * g->H * g->W / 2, 64);           // 64-pair tiles: each adds once per channel and statistic
-    const int s = tiles / 600;
-    return s < 1 ? 1 : (s > 8 ? 8 : s);
+    return stat_slots(ceil_div(g->N * g->H * g->W / 2, 64));        // 64-pair tiles: each adds once per channel and statistic
 }
 
 extern "C" int dynmm_conv2d_wino_fwd_stats(const float* x, const float* ut, const float* bias, float* y, double* stats,
@@ -827,8 +789,7 @@ extern "C" int dynmm_conv2d_wino_fwd_stats(const float* x, const float* ut, cons
     (void)hipGetLastError();
     if (!x || !ut || !y || !stats || !g || nslots < 1 || nslots > 64) return DYNMM_EINVAL;
     if (!dynmm_conv2d_wino_fwd_stats_supported(g)) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(stats)) & 7u) return DYNMM_EUNSUPPORTED;
+    if (!ptrs_aligned<16>(x, ut) || !ptrs_aligned<8>(y, stats)) return DYNMM_EUNSUPPORTED;
     WinoArgs a{};
     a.x = x; a.ut = ut; a.shift = bias; a.residual = nullptr; a.mask = nullptr; a.y = y; a.stats = stats; a.nslots = nslots;
     a.N = g->N; a.Ci = g->Ci; a.Co = g->Co; a.H = g->H; a.W = g->W;
@@ -843,14 +804,8 @@ extern "C" int dynmm_conv2d_wino_dgrad(const float* dy, const float* ut, const f
     if (!dy || !ut || !dx || !g) return DYNMM_EINVAL;
     const bool s2 = !wino_geom_ok(g, true) && wino_s2_geom_ok(g);
     if (!s2 && !wino_geom_ok(g, true)) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(accum)) & 7u)
-        return DYNMM_EUNSUPPORTED;
-    WinoArgs a{};
-    a.x = dy; a.ut = ut; a.shift = nullptr; a.residual = accum; a.mask = mask; a.y = dx;
-    a.N = g->N; a.Ci = g->Co; a.Co = g->Ci; a.H = g->H; a.W = g->W;         // the roles of the channel counts swap
-    a.CoS = (a.Co + 63) & ~63;
-    a.act = DYNMM_ACT_NONE;
-    a.Hin = g->Ho; a.Win = g->Wo;                                             // (stride 2: dy is half as high / wide as dx)
+    if (!ptrs_aligned<16>(dy, ut) || !ptrs_aligned<8>(dx, mask, accum)) return DYNMM_EUNSUPPORTED;
+    WinoArgs a = wino_dgrad_args(dy, ut, g);
+    a.residual = accum; a.mask = mask; a.y = dx;
     return launch_wino(a, g->KW == 1, true, (hipStream_t)stream, s2);
 }

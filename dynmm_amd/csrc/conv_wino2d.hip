@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "conv_igemm.h"
+#include "pack_desc.h"
 
 namespace dynmm {
 
@@ -45,14 +46,6 @@ struct Wino2dArgs {
     int TH, TW, MT;         // tile rows per image, tile columns, tiles
     int n_co_tiles, n_t_tiles;
 };
-
-__device__ __forceinline__ float row16_sum2d(float v) {          // sum over the lane's row of 16 lanes, in every lane of it
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));      // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));      // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true));     // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, true));     // row_mirror
-    return v;
-}
 
 template <bool DGRAD, bool TAIL, bool STATS>
 __global__ void __launch_bounds__(256, 2) conv_wino2d_kernel(const Wino2dArgs a) {
@@ -319,8 +312,8 @@ __global__ void __launch_bounds__(256, 2) conv_wino2d_kernel(const Wino2dArgs a)
                 float s1 = tvalid ? y00 + y01 : 0.f, s2 = tvalid ? fmaf(y00, y00, y01 * y01) : 0.f;
                 s1 += l1 ? y10 + y11 : 0.f;
                 s2 += l1 ? fmaf(y10, y10, y11 * y11) : 0.f;
-                s1 = row16_sum2d(s1);
-                s2 = row16_sum2d(s2);
+                s1 = row16_sum(s1);
+                s2 = row16_sum(s2);
                 if (l15 == 0) {
                     st_lds[(wave_t * 64 + cl) * 2 + 0] = s1;
                     st_lds[(wave_t * 64 + cl) * 2 + 1] = s2;
@@ -351,11 +344,11 @@ __device__ __forceinline__ float4 wino2d_u(const float* __restrict__ g, int tq, 
     return make_float4(gr[0], (gr[0] + gr[1] + gr[2]) * 0.5f, (gr[0] - gr[1] + gr[2]) * 0.5f, gr[2]);
 }
 
-__global__ void __launch_bounds__(256) wino2d_pack_kernel(const float* __restrict__ w, float4* __restrict__ ut,
-                                                          const float* __restrict__ scale, int Co, int Ci, int dgrad) {
+// element o = (k * 4 + tq) * Cs + c of one operand; sc: the folded factor of the row's output channel, or nullptr (1)
+__device__ __forceinline__ void wino2d_pack_one(const float* __restrict__ w, float4* __restrict__ ut, const float* __restrict__ scale,
+                                                int Co, int Ci, int dgrad, size_t o) {
     const int K = dgrad ? Co : Ci, Cr = dgrad ? Ci : Co, Cs = (Cr + 63) & ~63;
     const size_t total = (size_t)K * 4 * Cs;
-    const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (o >= total) return;
     const int c = (int)(o % Cs);
     const int tq = (int)((o / Cs) % 4);
@@ -365,33 +358,17 @@ __global__ void __launch_bounds__(256) wino2d_pack_kernel(const float* __restric
     ut[o] = wino2d_u(w + ((size_t)co * Ci + ci) * 9, tq, dgrad != 0, scale ? scale[co] : 1.f);
 }
 
-// Many filters in one launch (ops.PackedWeights): the descriptor layout of conv_wino.hip's wino_pack_multi (32 bytes).
-struct Wino2dPackDesc {
-    long long src, dst;
-    int Co, Ci, kk, blk0;      // kk: dgrad << 16
-};
+__global__ void __launch_bounds__(256) wino2d_pack_kernel(const float* __restrict__ w, float4* __restrict__ ut,
+                                                          const float* __restrict__ scale, int Co, int Ci, int dgrad) {
+    wino2d_pack_one(w, ut, scale, Co, Ci, dgrad, (size_t)blockIdx.x * 256 + threadIdx.x);
+}
 
+// Many filters in one launch (ops.PackedWeights)
 __global__ void __launch_bounds__(256) wino2d_pack_multi_kernel(const float* __restrict__ src_base, float* __restrict__ dst_base,
-                                                                const Wino2dPackDesc* __restrict__ desc, int ndesc) {
-    int lo = 0, hi = ndesc - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (desc[mid].blk0 <= (int)blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const Wino2dPackDesc d = desc[lo];
-    const int dgrad = (d.kk >> 16) & 1;
-    const int K = dgrad ? d.Co : d.Ci, Cr = dgrad ? d.Ci : d.Co, Cs = (Cr + 63) & ~63;
-    const size_t total = (size_t)K * 4 * Cs;
-    const size_t o = (size_t)((int)blockIdx.x - d.blk0) * 256 + threadIdx.x;
-    if (o >= total) return;
-    const int c = (int)(o % Cs);
-    const int tq = (int)((o / Cs) % 4);
-    const int k = (int)(o / ((size_t)Cs * 4));
-    float4* ut = reinterpret_cast<float4*>(dst_base + d.dst);
-    if (c >= Cr) { ut[o] = make_float4(0.f, 0.f, 0.f, 0.f); return; }
-    const int co = dgrad ? k : c, ci = dgrad ? c : k;
-    ut[o] = wino2d_u(src_base + d.src + ((size_t)co * d.Ci + ci) * 9, tq, dgrad != 0, 1.f);
+                                                                const WinoPackDesc* __restrict__ desc, int ndesc) {
+    const WinoPackDesc d = pack_desc_find(desc, ndesc);
+    wino2d_pack_one(src_base + d.src, reinterpret_cast<float4*>(dst_base + d.dst), nullptr, d.Co, d.Ci, (d.kk >> 16) & 1,
+                    (size_t)((int)blockIdx.x - d.blk0) * 256 + threadIdx.x);
 }
 
 // rows = output channels of the GEMM, red = its reduction channels (4 per stage, >= 3 stages): forward (Co, Ci), input
@@ -403,7 +380,7 @@ static bool wino2d_geom_ok(const dynmm_conv_geom* g, bool dgrad) {
     const int rows = dgrad ? g->Ci : g->Co, red = dgrad ? g->Co : g->Ci;
     if ((dgrad ? rows % 64 != 0 : (rows % 8 != 0 || rows < 24)) || red % 4 != 0 || red < 12) return false;
     if ((long long)g->N * g->H * g->W < 256) return false;
-    if ((double)g->N * (g->Ci > g->Co ? g->Ci : g->Co) * g->H * g->W >= 1073741824.0) return false;   // 32-bit byte offsets
+    if (!offsets_fit_32(g->N, g->Ci, g->Co, g->H, g->W)) return false;
     return true;
 }
 
@@ -438,7 +415,7 @@ extern "C" size_t dynmm_wino2d_packed_floats(int Co, int Ci) {
 extern "C" int dynmm_wino2d_pack(const float* w, float* ut, const float* scale, int Co, int Ci, int dgrad, void* stream) {
     (void)hipGetLastError();
     if (!w || !ut || Co <= 0 || Ci <= 0 || (scale && dgrad) || dgrad < 0 || dgrad > 1) return DYNMM_EINVAL;
-    if (reinterpret_cast<uintptr_t>(ut) & 15u) return DYNMM_EINVAL;
+    if (!ptrs_aligned<16>(ut)) return DYNMM_EINVAL;
     const int K = dgrad ? Co : Ci, Cs = ((dgrad ? Ci : Co) + 63) & ~63;
     const size_t total = (size_t)K * 4 * Cs;
     hipLaunchKernelGGL(wino2d_pack_kernel, dim3((unsigned)ceil_div_sz(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
@@ -454,14 +431,7 @@ extern "C" int dynmm_wino2d_pack_multi_blocks(int Co, int Ci, int dgrad) {
 
 extern "C" int dynmm_wino2d_pack_multi(const float* src_base, float* dst_base, const void* desc, int ndesc, int total_blocks,
                                        void* stream) {
-    (void)hipGetLastError();
-    if (!src_base || !dst_base || !desc || ndesc <= 0 || total_blocks <= 0) return DYNMM_EINVAL;
-    if (reinterpret_cast<uintptr_t>(dst_base) & 15u) return DYNMM_EINVAL;
-    static_assert(sizeof(Wino2dPackDesc) == 32, "descriptor layout is part of the ABI (4 x int64 words)");
-    hipLaunchKernelGGL(wino2d_pack_multi_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, src_base, dst_base,
-                       (const Wino2dPackDesc*)desc, ndesc);
-    DYNMM_LAUNCH_CHECK();
-    return DYNMM_OK;
+    return launch_wino_pack_multi(wino2d_pack_multi_kernel, src_base, dst_base, desc, ndesc, total_blocks, stream);
 }
 
 extern "C" int dynmm_conv2d_wino2d_fwd(const float* x, const float* ut, const float* bias, const float* residual, float* y,
@@ -471,9 +441,7 @@ extern "C" int dynmm_conv2d_wino2d_fwd(const float* x, const float* ut, const fl
     if (!act_is_known(act)) return DYNMM_EINVAL;
     if (!wino2d_geom_ok(g, false)) return DYNMM_EUNSUPPORTED;
     if (stats && (g->Co % 64 != 0 || residual || act != DYNMM_ACT_NONE || nslots < 1 || nslots > 64)) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(stats)) & 7u)
-        return DYNMM_EUNSUPPORTED;
+    if (!ptrs_aligned<16>(x, ut) || !ptrs_aligned<8>(y, residual, stats)) return DYNMM_EUNSUPPORTED;
     Wino2dArgs a{};
     a.x = x; a.ut = ut; a.shift = bias; a.residual = residual; a.mask = nullptr; a.y = y; a.stats = stats; a.nslots = nslots;
     a.N = g->N; a.Ci = g->Ci; a.Co = g->Co; a.H = g->H; a.W = g->W; a.act = act;
@@ -482,9 +450,7 @@ extern "C" int dynmm_conv2d_wino2d_fwd(const float* x, const float* ut, const fl
 
 extern "C" int dynmm_conv2d_wino2d_stats_slots(const dynmm_conv_geom* g) {
     if (!wino2d_geom_ok(g, false) || g->Co % 64 != 0) return 0;
-    const int tiles = ceil_div(g->N * ((g->H + 1) / 2) * (g->W / 2), 32);       // each adds once per channel and statistic
-    const int s = tiles / 600;
-    return s < 1 ? 1 : (s > 8 ? 8 : s);
+    return stat_slots(ceil_div(g->N * ((g->H + 1) / 2) * (g->W / 2), 32));      // tiles: each adds once per channel and statistic
 }
 
 extern "C" int dynmm_conv2d_wino2d_dgrad(const float* dy, const float* ut, const float* mask, const float* accum, float* dx,
@@ -492,9 +458,7 @@ extern "C" int dynmm_conv2d_wino2d_dgrad(const float* dy, const float* ut, const
     (void)hipGetLastError();
     if (!dy || !ut || !dx || !g) return DYNMM_EINVAL;
     if (!wino2d_geom_ok(g, true)) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ut)) & 15u) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(accum)) & 7u)
-        return DYNMM_EUNSUPPORTED;
+    if (!ptrs_aligned<16>(dy, ut) || !ptrs_aligned<8>(dx, mask, accum)) return DYNMM_EUNSUPPORTED;
     Wino2dArgs a{};
     a.x = dy; a.ut = ut; a.shift = nullptr; a.residual = accum; a.mask = mask; a.y = dx; a.stats = nullptr; a.nslots = 1;
     a.N = g->N; a.Ci = g->Co; a.Co = g->Ci; a.H = g->H; a.W = g->W; a.act = DYNMM_ACT_NONE;       // the channel roles swap

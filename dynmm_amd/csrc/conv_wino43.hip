@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "conv_igemm.h"
+#include "pack_desc.h"
 
 namespace dynmm {
 
@@ -362,41 +363,26 @@ __device__ __forceinline__ void wino43_u(float g0, float g1, float g2, float4& u
     u2 = make_float2(fmaf(-g1, 1.f / 12.f, fmaf(g0, 1.f / 24.f, g2 * (1.f / 6.f))), g2);
 }
 
-struct Wino43PackDesc {
-    long long src, dst;      // float offsets from the two bases (dst: the record's ut4; its ut2 follows the ut4 block)
-    int Co, Ci, kk, blk0;    // kk = KH | KW << 8
-};
-
-__global__ void __launch_bounds__(256) wino43_pack_multi_kernel(const float* __restrict__ src_base, float* __restrict__ dst_base,
-                                                                const Wino43PackDesc* __restrict__ desc, int ndesc) {
-    int lo = 0, hi = ndesc - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (desc[mid].blk0 <= (int)blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const Wino43PackDesc d = desc[lo];
-    const size_t total = (size_t)d.Co * d.Ci;
-    const size_t o = (size_t)((int)blockIdx.x - d.blk0) * 256 + threadIdx.x;
+// one filter: o = co * Ci + ci
+__device__ __forceinline__ void wino43_pack_one(const float* __restrict__ w, float* __restrict__ ut, int Co, int Ci, size_t o) {
+    const size_t total = (size_t)Co * Ci;
     if (o >= total) return;
-    const float* g = src_base + d.src + o * 3;    // o = co * Ci + ci
+    const float* g = w + o * 3;
     float4 u4;
     float2 u2;
     wino43_u(g[2], g[1], g[0], u4, u2);           // flipped taps
-    reinterpret_cast<float4*>(dst_base + d.dst)[o] = u4;
-    reinterpret_cast<float2*>(dst_base + d.dst + total * 4)[o] = u2;
+    reinterpret_cast<float4*>(ut)[o] = u4;
+    reinterpret_cast<float2*>(ut + total * 4)[o] = u2;
+}
+
+__global__ void __launch_bounds__(256) wino43_pack_multi_kernel(const float* __restrict__ src_base, float* __restrict__ dst_base,
+                                                                const WinoPackDesc* __restrict__ desc, int ndesc) {
+    const WinoPackDesc d = pack_desc_find(desc, ndesc);
+    wino43_pack_one(src_base + d.src, dst_base + d.dst, d.Co, d.Ci, (size_t)((int)blockIdx.x - d.blk0) * 256 + threadIdx.x);
 }
 
 __global__ void __launch_bounds__(256) wino43_pack_kernel(const float* __restrict__ w, float* __restrict__ ut, int Co, int Ci) {
-    const size_t total = (size_t)Co * Ci;
-    const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (o >= total) return;
-    const float* g = w + o * 3;                   // o = co * Ci + ci
-    float4 u4;
-    float2 u2;
-    wino43_u(g[2], g[1], g[0], u4, u2);
-    reinterpret_cast<float4*>(ut)[o] = u4;
-    reinterpret_cast<float2*>(ut + total * 4)[o] = u2;
+    wino43_pack_one(w, ut, Co, Ci, (size_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 static bool wino43_geom_ok(const dynmm_conv_geom* g) {
@@ -407,7 +393,7 @@ static bool wino43_geom_ok(const dynmm_conv_geom* g) {
     if (g->W % 4 != 0 || g->W < 4 || g->H < 2) return false;
     if (g->Ci % 64 != 0 || g->Co % 8 != 0 || g->Co < 24) return false;       // rows = Ci (64-row tile), reduction = Co
     if ((long long)g->N * g->H * g->W < 256) return false;
-    if ((double)g->N * (g->Ci > g->Co ? g->Ci : g->Co) * ((g->H + 3) / 4 * 4) * g->W >= 1073741824.0) return false;
+    if (!offsets_fit_32(g->N, g->Ci, g->Co, (g->H + 3) / 4 * 4, g->W)) return false;
     return true;
 }
 
@@ -426,7 +412,7 @@ extern "C" int dynmm_wino43_pack(const float* w, float* ut, int Co, int Ci, int 
     (void)hipGetLastError();
     if (!w || !ut || Co <= 0 || Ci <= 0) return DYNMM_EINVAL;
     if (!(KH == 1 && KW == 3)) return DYNMM_EUNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(ut) & 15u) return DYNMM_EINVAL;
+    if (!ptrs_aligned<16>(ut)) return DYNMM_EINVAL;
     const size_t total = dynmm_wino43_packed_floats(Co, Ci, KH, KW) / 6;
     hipLaunchKernelGGL(wino43_pack_kernel, dim3((unsigned)ceil_div_sz(total, 256)), dim3(256), 0, (hipStream_t)stream, w, ut, Co, Ci);
     DYNMM_LAUNCH_CHECK();
@@ -439,14 +425,7 @@ extern "C" int dynmm_wino43_pack_multi_blocks(int Co, int Ci, int KH, int KW) {
 
 extern "C" int dynmm_wino43_pack_multi(const float* src_base, float* dst_base, const void* desc, int ndesc, int total_blocks,
                                        void* stream) {
-    (void)hipGetLastError();
-    if (!src_base || !dst_base || !desc || ndesc <= 0 || total_blocks <= 0) return DYNMM_EINVAL;
-    if (reinterpret_cast<uintptr_t>(dst_base) & 15u) return DYNMM_EINVAL;
-    static_assert(sizeof(Wino43PackDesc) == 32, "descriptor layout is part of the ABI (4 x int64 words)");
-    hipLaunchKernelGGL(wino43_pack_multi_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, src_base, dst_base,
-                       (const Wino43PackDesc*)desc, ndesc);
-    DYNMM_LAUNCH_CHECK();
-    return DYNMM_OK;
+    return launch_wino_pack_multi(wino43_pack_multi_kernel, src_base, dst_base, desc, ndesc, total_blocks, stream);
 }
 
 extern "C" int dynmm_conv2d_wino43_dgrad(const float* dy, const float* ut, const float* mask, const float* accum, float* dx,
@@ -454,9 +433,7 @@ extern "C" int dynmm_conv2d_wino43_dgrad(const float* dy, const float* ut, const
     (void)hipGetLastError();
     if (!dy || !ut || !dx || !g) return DYNMM_EINVAL;
     if (!wino43_geom_ok(g)) return DYNMM_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ut) | reinterpret_cast<uintptr_t>(dx) |
-         reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(accum)) & 15u)
-        return DYNMM_EUNSUPPORTED;
+    if (!ptrs_aligned<16>(dy, ut, dx, mask, accum)) return DYNMM_EUNSUPPORTED;
     Wino43Args a{};
     a.x = dy; a.ut4 = ut; a.ut2 = ut + (size_t)g->Co * g->Ci * 4; a.residual = accum; a.mask = mask; a.y = dx;
     a.N = g->N; a.Ci = g->Co; a.Co = g->Ci; a.H = g->H; a.W = g->W;          // the roles of the channel counts swap

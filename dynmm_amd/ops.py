@@ -77,8 +77,16 @@ def _operand(op, t, name, shape=None):
 WINO = 'all'
 WINO_DGRAD = '43h'
 CONV_BN_STATS = True
-_WINO_OK = {}
-_WINO43_OK = {}
+_SUPPORTED = {}          # (library function, geometry, extra arguments) -> the library's answer
+
+
+def _supported(fn, g, *extra):
+    """the library's `fn(geometry, *extra)`, asked once per geometry"""
+    key = (fn, g.N, g.Ci, g.H, g.W, g.Co, g.Ho, g.Wo, g.KH, g.KW, g.SH, g.SW, g.PH, g.PW, g.c_split) + extra
+    r = _SUPPORTED.get(key)
+    if r is None:
+        r = _SUPPORTED[key] = int(getattr(_lib(), fn)(C.byref(g), *extra))
+    return r
 
 
 def _wino43(g):
@@ -88,14 +96,7 @@ def _wino43(g):
     # (round 5, alternating runs: F(4,3) only where its quad tiles fill the chip — C <= 128 / C <= 256 — 63.94 / 64.07 ms against
     # 63.75 with F(4,3) on every horizontal launch: where it is slower in isolation (C = 512: 124 against 111 us) the half of the
     # matrix pipe it leaves goes to the weight-gradient streams)
-    key = (g.N, g.Ci, g.H, g.W, g.Co, g.KH, g.KW, g.SH, g.SW, g.PH, g.PW, g.c_split)
-    ok = _WINO43_OK.get(key)
-    if ok is None:
-        ok = _WINO43_OK[key] = bool(_lib().dynmm_conv2d_wino43_supported(C.byref(g)))
-    return ok
-
-
-_WINO2D_OK = {}
+    return bool(_supported('dynmm_conv2d_wino43_supported', g))
 
 
 def _wino2d(g, dgrad, x2=None, infer=False):
@@ -105,11 +106,7 @@ def _wino2d(g, dgrad, x2=None, infer=False):
         return False
     if not infer and ((WINO == 'dgrad' and not dgrad) or (WINO == 'fwd' and dgrad)):
         return False
-    key = (g.N, g.Ci, g.H, g.W, g.Co, g.SH, g.SW, g.PH, g.PW, g.c_split, bool(dgrad))
-    ok = _WINO2D_OK.get(key)
-    if ok is None:
-        ok = _WINO2D_OK[key] = bool(_lib().dynmm_conv2d_wino2d_supported(C.byref(g), int(bool(dgrad))))
-    return ok
+    return bool(_supported('dynmm_conv2d_wino2d_supported', g, int(bool(dgrad))))
 
 
 def _wino(g, dgrad, x2=None, infer=False):
@@ -118,12 +115,8 @@ def _wino(g, dgrad, x2=None, infer=False):
         return False
     if not infer and ((WINO == 'dgrad' and not dgrad) or (WINO == 'fwd' and dgrad)):
         return False
-    key = (g.N, g.Ci, g.H, g.W, g.Co, g.KH, g.KW, g.SH, g.SW, g.PH, g.PW, g.c_split, bool(dgrad))
-    ok = _WINO_OK.get(key)
-    if ok is None:
-        # 1: stride-1 three-tap / 3x3 (Winograd); 2 (input gradient only): stride-2 three-tap (polyphase form of the same kernel)
-        ok = _WINO_OK[key] = int(_lib().dynmm_conv2d_wino_supported(C.byref(g), int(bool(dgrad))))
-    return ok
+    # 1: stride-1 three-tap / 3x3 (Winograd); 2 (input gradient only): stride-2 three-tap (polyphase form of the same kernel)
+    return _supported('dynmm_conv2d_wino_supported', g, int(bool(dgrad)))
 
 
 # A pass of a convolution runs on ONE kernel family, its route, and reads ONE re-laid weight: the operand kind of that route
@@ -154,9 +147,34 @@ def _dgrad_route(g, x2):
     return 'wino_s2' if w == 2 else 'wino'       # (stride 2: the polyphase form, an operand of its own)
 
 
-# kind -> the `dgrad` argument of its pack (1-D: 0 forward | 1 input gradient | 2 stride-2 input gradient, the polyphase operand)
-_WINO_PACK_ARG = {'wino_fwd': 0, 'wino_dgrad': 1, 'wino_dgrad_s2': 2}
-_WINO2D_PACK_ARG = {'wino2d_fwd': 0, 'wino2d_dgrad': 1}
+# The Winograd pack families, each described once.  kinds: operand kind -> the `dgrad` argument of its pack (F(2,3): 0 forward |
+# 1 input gradient | 2 stride-2 input gradient, the polyphase operand; F(4,3) packs the input gradient's operand only and takes
+# none).  floats(lib, Co, Ci, KH, KW): a slot's size; pack(lib, w, ut, scale, Co, Ci, KH, KW, arg, stream): the per-tensor pack;
+# blocks(lib, Co, Ci, KH, KW, arg): thread blocks of one tensor in the multi-tensor launch dynmm_<name>_pack_multi; word(KH, KW,
+# arg): the low half of its descriptor's fourth word (csrc/pack_desc.h).
+_PackFamily = collections.namedtuple('_PackFamily', 'name kinds floats pack blocks word')
+_PACK_FAMILIES = (
+    _PackFamily('wino', {'wino_fwd': 0, 'wino_dgrad': 1, 'wino_dgrad_s2': 2},
+                lambda lib, Co, Ci, KH, KW: lib.dynmm_wino_packed_floats(Co, Ci, KH, KW),
+                lambda lib, w, ut, scale, Co, Ci, KH, KW, arg, st: lib.dynmm_wino_pack(w, ut, scale, Co, Ci, KH, KW, arg, st),
+                lambda lib, Co, Ci, KH, KW, arg: lib.dynmm_wino_pack_multi_blocks(Co, Ci, KH, KW),
+                lambda KH, KW, arg: KH | (KW << 8) | (arg << 16)),
+    _PackFamily('wino43', {'wino43_dgrad': None},
+                lambda lib, Co, Ci, KH, KW: lib.dynmm_wino43_packed_floats(Co, Ci, KH, KW),
+                lambda lib, w, ut, scale, Co, Ci, KH, KW, arg, st: lib.dynmm_wino43_pack(w, ut, Co, Ci, KH, KW, st),
+                lambda lib, Co, Ci, KH, KW, arg: lib.dynmm_wino43_pack_multi_blocks(Co, Ci, KH, KW),
+                lambda KH, KW, arg: KH | (KW << 8)),
+    _PackFamily('wino2d', {'wino2d_fwd': 0, 'wino2d_dgrad': 1},
+                lambda lib, Co, Ci, KH, KW: lib.dynmm_wino2d_packed_floats(Co, Ci),
+                lambda lib, w, ut, scale, Co, Ci, KH, KW, arg, st: lib.dynmm_wino2d_pack(w, ut, scale, Co, Ci, arg, st),
+                lambda lib, Co, Ci, KH, KW, arg: lib.dynmm_wino2d_pack_multi_blocks(Co, Ci, arg),
+                lambda KH, KW, arg: arg << 16),
+)
+
+
+def _family_kinds(kinds):
+    """(family, kind, pack argument) of every Winograd operand among `kinds`, in the table's order"""
+    return [(f, kind, arg) for f in _PACK_FAMILIES for kind, arg in f.kinds.items() if kind in kinds]
 
 
 def _pack_operands(weight, g, kinds, scale=None):
@@ -173,15 +191,8 @@ def _pack_operands(weight, g, kinds, scale=None):
         wp = new('fwd', lib.dynmm_packed_weight_floats(*dims, 0)) if 'fwd' in kinds else None
         wpd = new('dgrad', lib.dynmm_packed_weight_floats(*dims, 1)) if 'dgrad' in kinds else None
         L.check(lib.dynmm_pack_weight(_p(weight), wp, wpd, *dims, st), 'pack_weight')
-    for kind in kinds:
-        if kind in _WINO_PACK_ARG:
-            L.check(lib.dynmm_wino_pack(_p(weight), new(kind, lib.dynmm_wino_packed_floats(*dims)), _p(scale), *dims,
-                                        _WINO_PACK_ARG[kind], st), 'wino_pack')
-        elif kind == 'wino43_dgrad':
-            L.check(lib.dynmm_wino43_pack(_p(weight), new(kind, lib.dynmm_wino43_packed_floats(*dims)), *dims, st), 'wino43_pack')
-        elif kind in _WINO2D_PACK_ARG:
-            L.check(lib.dynmm_wino2d_pack(_p(weight), new(kind, lib.dynmm_wino2d_packed_floats(g.Co, g.Ci)), _p(scale), g.Co, g.Ci,
-                                          _WINO2D_PACK_ARG[kind], st), 'wino2d_pack')
+    for f, kind, arg in _family_kinds(kinds):
+        L.check(f.pack(lib, _p(weight), new(kind, f.floats(lib, *dims)), _p(scale), *dims, arg, st), f.name + '_pack')
     return out
 
 
@@ -811,7 +822,9 @@ class PackedWeights:
         ents = list(self.reg.values())
         dev = ents[0].weight.device
         base = min(e.weight.data_ptr() for e in ents)
-        off, blk, wblk, w43blk, w2blk, rows, wrows, w43rows, w2rows = 0, 0, 0, 0, 0, [], [], [], []
+        off = 0
+        rows = {name: [] for name in ('pack_weight',) + tuple(f.name + '_pack' for f in _PACK_FAMILIES)}    # in launch order
+        blk = dict.fromkeys(rows, 0)
         spans = {}
         for w, Co, Ci, KH, KW, kinds in ents:
             src = (w.data_ptr() - base) // 4
@@ -824,36 +837,21 @@ class PackedWeights:
                 ndg = lib.dynmm_packed_weight_floats(Co, Ci, KH, KW, 1) if nd else 0
                 dstf, dstd = off, (off + _up4(nf) if nd else -1)
                 off += _up4(nf) + _up4(ndg)      # rows stay 16-byte aligned (the kernels' dwordx4 path)
-                rows.append([src, dstf, dstd, Co | (Ci << 32), (KH * KW) | (blk << 32)])
+                rows['pack_weight'].append([src, dstf, dstd, Co | (Ci << 32), (KH * KW) | (blk['pack_weight'] << 32)])
                 span['fwd'] = (dstf, nf)
                 if nd:
                     span['dgrad'] = (dstd, ndg)
-                blk += lib.dynmm_pack_weight_multi_blocks(Co, Ci, KH, KW, int(nd))
-            for kind, dgrad in _WINO_PACK_ARG.items():
-                if kind in kinds:
-                    nu = lib.dynmm_wino_packed_floats(Co, Ci, KH, KW)
-                    wrows.append([src, off, Co | (Ci << 32), KH | (KW << 8) | (dgrad << 16) | (wblk << 32)])
-                    span[kind] = (off, nu)
-                    off += nu                    # a multiple of 4 floats
-                    wblk += lib.dynmm_wino_pack_multi_blocks(Co, Ci, KH, KW)
-            if 'wino43_dgrad' in kinds:
-                nu43 = lib.dynmm_wino43_packed_floats(Co, Ci, KH, KW)
-                w43rows.append([src, off, Co | (Ci << 32), KH | (KW << 8) | (w43blk << 32)])
-                span['wino43_dgrad'] = (off, nu43)
-                off += _up4(nu43)
-                w43blk += lib.dynmm_wino43_pack_multi_blocks(Co, Ci, KH, KW)
-            for kind, dgrad in _WINO2D_PACK_ARG.items():
-                if kind in kinds:
-                    nu2 = lib.dynmm_wino2d_packed_floats(Co, Ci)
-                    w2rows.append([src, off, Co | (Ci << 32), (dgrad << 16) | (w2blk << 32)])
-                    span[kind] = (off, nu2)
-                    off += nu2                   # a multiple of 4 floats
-                    w2blk += lib.dynmm_wino2d_pack_multi_blocks(Co, Ci, dgrad)
+                blk['pack_weight'] += lib.dynmm_pack_weight_multi_blocks(Co, Ci, KH, KW, int(nd))
+            for f, kind, arg in _family_kinds(kinds):
+                name, n = f.name + '_pack', f.floats(lib, Co, Ci, KH, KW)
+                rows[name].append([src, off, Co | (Ci << 32), f.word(KH, KW, arg) | (blk[name] << 32)])
+                span[kind] = (off, n)
+                off += _up4(n)                   # (F(4,3): 6 floats per filter; the other two families' slots are multiples of 4)
+                blk[name] += f.blocks(lib, Co, Ci, KH, KW, arg)
         self.arena = torch.empty(off, device=dev, dtype=torch.float32)
         self.base = base
-        self.launches = [(name, torch.tensor(r, dtype=torch.int64).to(dev), len(r), b) for name, r, b in
-                         (('pack_weight_multi', rows, blk), ('wino_pack_multi', wrows, wblk), ('wino43_pack_multi', w43rows, w43blk),
-                          ('wino2d_pack_multi', w2rows, w2blk)) if r]
+        self.launches = [(name + '_multi', torch.tensor(r, dtype=torch.int64).to(dev), len(r), blk[name])
+                         for name, r in rows.items() if r]
         self.slots = {k: {kind: self.arena[o:o + n] for kind, (o, n) in span.items()} for k, span in spans.items()}
         self.dirty = False
 

@@ -1132,6 +1132,152 @@ def test_stride1_and_stride2_winograd_input_gradient_operands_are_distinct_kinds
     assert not torch.equal(pw.lookup(w1, ('wino_dgrad',))['wino_dgrad'], pw.lookup(w2, ('wino_dgrad_s2',))['wino_dgrad_s2'])
 
 
+# ---- closed-form references of the packed operand layouts, from the layout formulas in the kernels' comments --------------------
+# Each returns (ref, A, exact), flat over the LIVE part of the operand: the float64 value of every element, the same transform
+# applied to |g| with the absolute values of its coefficients (0 on padding), and which elements are pure re-layouts (padding
+# zeros, copied taps of the polyphase operand, both direct layouts) that must equal the reference bit for bit.
+_U = 2.0 ** -24          # unit roundoff of float32
+
+
+def _up(v, m):
+    return (v + m - 1) // m * m
+
+
+def _ref_pack_direct(w, dgrad):
+    """conv_igemm.hip: wf[(tap*CiR + ci)*CoP + co], wd[(tap*CoR + co)*CiP + ci]; rows per tap rounded up to 16 for 8 <= C,
+    C % 16 != 0 (round_k), row length rounded up to 4; every padding element 0"""
+    Co, Ci, KH, KW = w.shape
+    rk = lambda c: _up(c, 16) if c >= 8 and c % 16 else c
+    g = w.reshape(Co, Ci, KH * KW)
+    if dgrad:
+        out = np.zeros((KH * KW, rk(Co), _up(Ci, 4)), np.float32)
+        out[:, :Co, :Ci] = g.transpose(2, 0, 1)
+    else:
+        out = np.zeros((KH * KW, rk(Ci), _up(Co, 4)), np.float32)
+        out[:, :Ci, :Co] = g.transpose(2, 1, 0)
+    return out.ravel().astype(np.float64), np.abs(out.ravel()).astype(np.float64), np.ones(out.size, bool)
+
+
+def _pad_rows(u, axis, exact_all=False):
+    """rows (the operand's output channels, `axis`) padded with zeros to the 64-row tile; -> (padded, which elements are padding)"""
+    shape = list(u.shape)
+    shape[axis] = _up(shape[axis], 64)
+    out, pad = np.zeros(shape), np.ones(shape, bool)
+    sl = tuple(slice(0, n) for n in u.shape)
+    out[sl], pad[sl] = u, exact_all
+    return out.ravel(), pad.ravel()
+
+
+def _ref_pack_f23(w, arg, scale=None):
+    """conv_wino.hip: ut[K][C rounded up to 64][4] with (K, C) = (Ci, Co) forward | (Co, Ci) input gradient (taps flipped);
+    U = (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2); arg 2 (stride-2 input gradient): (g1, g2, g0, 0), no transform"""
+    Co, Ci = w.shape[:2]
+    g = w.reshape(Co, Ci, 3).astype(np.float64)
+    if scale is not None:
+        g = g * scale.astype(np.float64)[:, None, None]
+    t = g.transpose(1, 0, 2) if arg == 0 else g
+    if arg == 2:
+        u = np.stack([t[..., 1], t[..., 2], t[..., 0], np.zeros(t.shape[:2])], -1)
+        ref, exact = _pad_rows(u, 1, exact_all=True)
+        return ref, np.abs(ref), exact
+    if arg == 1:
+        t = t[..., ::-1]
+    t0, t1, t2 = t[..., 0], t[..., 1], t[..., 2]
+    a0, a1, a2 = np.abs(t0), np.abs(t1), np.abs(t2)
+    ref, exact = _pad_rows(np.stack([t0, (t0 + t1 + t2) / 2, (t0 - t1 + t2) / 2, t2], -1), 1)
+    return ref, _pad_rows(np.stack([a0, (a0 + a1 + a2) / 2, (a0 + a1 + a2) / 2, a2], -1), 1)[0], exact
+
+
+def _ref_pack_f43(w):
+    """conv_wino43.hip: ut4 [Co][Ci][4] then ut2 [Co][Ci][2] of the flipped taps g:
+    U = g0/4 | -(g0+g1+g2)/6 | -(g0-g1+g2)/6 | g0/24+g1/12+g2/6 | g0/24-g1/12+g2/6 | g2"""
+    Co, Ci = w.shape[:2]
+    t = w.reshape(Co, Ci, 3).astype(np.float64)[..., ::-1]
+    t0, t1, t2 = t[..., 0], t[..., 1], t[..., 2]
+    a0, a1, a2 = np.abs(t0), np.abs(t1), np.abs(t2)
+    u = [t0 / 4, -(t0 + t1 + t2) / 6, -(t0 - t1 + t2) / 6, t0 / 24 + t1 / 12 + t2 / 6, t0 / 24 - t1 / 12 + t2 / 6, t2]
+    a = [a0 / 4, (a0 + a1 + a2) / 6, (a0 + a1 + a2) / 6, a0 / 24 + a1 / 12 + a2 / 6, a0 / 24 + a1 / 12 + a2 / 6, a2]
+    flat = lambda v: np.concatenate([np.stack(v[:4], -1).ravel(), np.stack(v[4:], -1).ravel()])
+    return flat(u), flat(a), np.zeros(6 * Co * Ci, bool)
+
+
+def _ref_pack_f2x2(w, arg, scale=None):
+    """conv_wino2d.hip: ut[K][4 tq][C rounded up to 64][4] = (G g G^T)[tq][j] with (K, C) = (Ci, Co) forward | (Co, Ci) input
+    gradient (filter flipped along both axes); G = the F(2,3) matrix"""
+    g = w.astype(np.float64)
+    if scale is not None:
+        g = g * scale.astype(np.float64)[:, None, None, None]
+    t = g.transpose(1, 0, 2, 3) if arg == 0 else g[:, :, ::-1, ::-1]
+    G = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]])
+    ref, exact = _pad_rows(np.einsum('ia,kcab,jb->kicj', G, t, G), 2)
+    return ref, _pad_rows(np.einsum('ia,kcab,jb->kicj', np.abs(G), np.abs(t), np.abs(G)), 2)[0], exact
+
+
+def test_packed_operand_layouts_match_a_closed_form_reference(ops):
+    """Every operand kind, from the per-convolution pack (ops._pack_operands) AND from the step's multi-tensor launches
+    (ops.PackedWeights, two or more weights per family, so every launch searches its descriptors across a first-workgroup
+    boundary), against a numpy reference of the layout written from the kernels' comments, independent of both.
+      * pure re-layouts (both direct layouts, every zero of the padding, the polyphase operand (g1, g2, g0, 0)): bit-equal;
+      * transformed values: |got - ref| <= n * 2^-24 * A against the reference in float64, A = the transform of |g| with the
+        absolute coefficients, n = the float32 roundings on the transform's longest path:
+          F(2,3)      n = 2: the two additions of (g0 +- g1 + g2) (the halving is exact); + 1 with a folded scale (g * sc);
+          F(4,3)      n = 4: the rounded constant 1/6 and its product g2 * (1/6), then the two fused multiply-adds that add
+                      g0 * (1/24) and g1 * (1/12) (their constants and roundings lie on shorter paths); likewise
+                      s = g0 + g2, s +- g1, the constant 1/6, the product;
+          F(2x2,3x3)  n = 4: two additions down the columns, two along the rows; + 1 with a folded scale;
+      * the arena's slot equals the per-convolution pack bit for bit over its live part (K * padded rows * 4 floats, x 4 for
+        the 2-D family; what follows in a slot is written by neither)."""
+    from dynmm_amd import lib as L
+    cases = [   # weight shape, {kind: (reference, n)}
+        ((40, 24, 3, 3), {'fwd': (lambda w: _ref_pack_direct(w, 0), 0), 'dgrad': (lambda w: _ref_pack_direct(w, 1), 0)}),
+        ((33, 65, 1, 1), {'fwd': (lambda w: _ref_pack_direct(w, 0), 0)}),
+        ((6, 3, 7, 7), {'fwd': (lambda w: _ref_pack_direct(w, 0), 0), 'dgrad': (lambda w: _ref_pack_direct(w, 1), 0)}),
+        ((40, 24, 1, 3), {'wino_fwd': (lambda w: _ref_pack_f23(w, 0), 2)}),
+        ((24, 64, 3, 1), {'wino_dgrad': (lambda w: _ref_pack_f23(w, 1), 2)}),
+        ((24, 64, 3, 1), {'wino_dgrad_s2': (lambda w: _ref_pack_f23(w, 2), 0)}),
+        ((24, 64, 1, 3), {'wino43_dgrad': (_ref_pack_f43, 4)}),
+        ((32, 64, 1, 3), {'wino43_dgrad': (_ref_pack_f43, 4)}),
+        ((40, 12, 3, 3), {'wino2d_fwd': (lambda w: _ref_pack_f2x2(w, 0), 4)}),
+        ((12, 64, 3, 3), {'wino2d_dgrad': (lambda w: _ref_pack_f2x2(w, 1), 4)}),
+    ]
+
+    def check(got, ref, A, exact, n, tag):
+        got = got.cpu().numpy()[:ref.size]
+        assert got.size == ref.size and exact.all() == (n == 0), tag
+        same_bits = got.view(np.int32) == ref.astype(np.float32).view(np.int32)
+        assert same_bits[exact].all(), (tag, 're-layout', int((~same_bits[exact]).sum()))
+        err, bound = np.abs(got.astype(np.float64) - ref), n * _U * A
+        print(f'{tag}: n = {n}, max |got - ref| / (2^-24 A) = {(err[A > 0] / (_U * A[A > 0])).max():.3f}')
+        assert (err <= bound).all(), (tag, float((err - bound).max()), int((err > bound).argmax()))
+
+    ws = [torch.nn.Parameter(rnd(*shape, seed=i).cuda()) for i, (shape, _) in enumerate(cases)]
+    geoms = [L.ConvGeom(2, s[1], 16, 16, s[0], 16, 16, s[2], s[3], 1, 1, s[2] // 2, s[3] // 2, s[1]) for s, _ in cases]
+    pw = ops.PackedWeights()
+    for w, g, (_, kinds) in zip(ws, geoms, cases):
+        pw.register(w, g, tuple(kinds))
+    pw.pack()
+    assert [(name, n) for name, _, n, _ in pw.launches] == [('pack_weight_multi', 3), ('wino_pack_multi', 3),
+                                                            ('wino43_pack_multi', 2), ('wino2d_pack_multi', 2)]
+    for w, g, (shape, kinds) in zip(ws, geoms, cases):
+        single = ops._pack_operands(w, g, tuple(kinds))
+        multi = pw.lookup(w, tuple(kinds))
+        assert multi is not None and set(single) == set(multi) == set(kinds), shape
+        wn = w.detach().cpu().numpy()
+        for kind, (reference, n) in kinds.items():
+            ref, A, exact = reference(wn)
+            check(single[kind], ref, A, exact, n, (shape, kind))
+            live = ref.size
+            assert single[kind].numel() >= live and multi[kind].numel() >= live, (shape, kind)
+            assert torch.equal(multi[kind][:live].view(torch.int32), single[kind][:live].view(torch.int32)), (shape, kind)
+    # the folded scale of the inference forward: per-convolution packs only
+    for i, kind, reference in ((3, 'wino_fwd', _ref_pack_f23), (8, 'wino2d_fwd', _ref_pack_f2x2)):
+        scale = (rnd(cases[i][0][0], seed=20 + i) * 0.5 + 1.5).cuda()
+        ref, A, exact = reference(ws[i].detach().cpu().numpy(), 0, scale.cpu().numpy())
+        check(ops._pack_operands(ws[i], geoms[i], (kind,), scale)[kind], ref, A, exact, cases[i][1][kind][1] + 1,
+              (cases[i][0], kind, 'scale'))
+    torch.cuda.synchronize()
+
+
 def test_fused_eval_cache_follows_parameter_changes(ops):
     """conv2d_fused_eval caches the packed weights / folded BN per layer; every way the tensors can change
     (in-place torch ops, a training forward that rewrites the running statistics inside our kernel, a new
